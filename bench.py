@@ -12,7 +12,13 @@ mel frames), forced Ts=250 speech tokens (5.0 s -> Tm=430 frames -> L=110080 sam
 LM decode -> flow matching (10 Euler steps x CFG) -> HiFT vocoder.  Weights are seeded random-init at
 the CosyVoice-300M shapes (no checkpoints exist offline), inputs are resident in HBM when the timed
 region starts, the waveform stays on the GPU.  value = synthesized audio seconds / wall seconds,
-whole job.  The retrieval leg is additionally reported as queries/s (``knn_qps``).
+whole job.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds everything
+else the benchmark measures or checks after the timed steps: the retrieval leg as queries/s (``knn_qps``),
+oracle comparisons, rooflines, the host-I/O, co-batched and 24 kHz variants, BASELINE's other
+configurations, the side probes and the CPU baseline.  ``--dump-outputs DIR`` writes what the last timed
+step computed (style ids and scores, speech tokens, mel, waveform) as DIR/<name>.npy.
 """
 import argparse
 import dataclasses
@@ -168,6 +174,24 @@ def emit_json(obj):
     out = json_only_stdout()
     out.write(json.dumps(obj) + "\n")
     out.flush()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write every array of `arrays` ({name: tensor}) as out_dir/<name>.npy: floating point as float32, integers (ids, tokens) as
+    float64, which holds them exactly.  An array larger than its share of `budget` is replaced by a fixed, seeded sample of its
+    elements (flattened, in order), so that two runs with the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def free_port():
@@ -381,7 +405,7 @@ def knn_stress(args, dev, traffic_table):
 
 
 def run_side(args, which, dev, dist, rank, world, cfg, weights, eng=None, steps=1, warmup=1, traffic_table=None):
-    """BASELINE.json's other configurations, measured with the default line's protocol (W untimed warm-up steps, K timed steps between
+    """BASELINE.json's other configurations (--full), measured with the headline's protocol (W untimed warm-up steps, K timed steps between
     barrier + synchronize, MAX over ranks).  Returns the record on rank 0 (None elsewhere).
       config3  64 long-form lines = 384 text segments (Tt = 64, Ts = 250: 30 s per line) per step, as twelve 32-row batches through
                the stream pipeline; weak scaling (every rank its own 64 lines).  tts_with_style_and_timbre.py:91-95.
@@ -582,7 +606,7 @@ def run_side(args, which, dev, dist, rank, world, cfg, weights, eng=None, steps=
 
 
 def side_extras(args, dev, cfg, eng):
-    """Measurements of the rows next to the path that ride in the default line: filled in by the functions below as
+    """Measurements of the rows next to the path that ride in the --full line: filled in by the functions below as
     those rows are measured (rank 0 only, bounded to a few seconds each)."""
     out = {}
     for name, fn in (("embedder", bench_embedder), ("streaming", bench_streaming)):
@@ -803,8 +827,8 @@ def bench_streaming(args, dev, cfg, eng):
 
 
 def side_workload(args, which, dev, dist, rank, world):
-    """`--workload config3|config4|config5`: one side configuration as a line of its own, with the default line's JSON schema (the default
-    `python bench.py` = BASELINE configs[1] carries bounded passes of all three under `side_workloads`)."""
+    """`--workload config3|config4|config5`: one side configuration as a line of its own, with the headline line's JSON schema (`python bench.py
+    --full` = BASELINE configs[1] carries bounded passes of all three under `side_workloads`; the CPU baseline needs --full here too)."""
     from astts.synth.config import SynthConfig
     from astts.synth.weights import make_all
 
@@ -821,7 +845,7 @@ def side_workload(args, which, dev, dist, rank, world):
                "config": {"workload": r["workload"], "parallelism": f"dp{world}"},
                "side_measurement": f"--workload {which}: NOT the headline line (python bench.py = BASELINE configs[1])"}
         res.update({k: v for k, v in r.items() if k not in res and k != "workload"})
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             bank16 = make_config2_bank(args.bank_rows, args.dim)
             res["cpu_baseline"] = cpu_baseline(cfg, weights, bank16, make_queries(bank16, 8, seed=0), args.topk)
         emit_json(res)
@@ -841,6 +865,9 @@ def main():
     ap.add_argument("--prompt-tokens", type=int, default=150)
     ap.add_argument("--speech-tokens", type=int, default=250)
     ap.add_argument("--sample-rate", type=int, default=22050)
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run every other measurement and check (see the module "
+                    "docstring); the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-io", action="store_true", help="skip the host-I/O-inclusive side pass (value_with_host_io, frontend_ms)")
     ap.add_argument("--embedder-layers", type=int, default=0, help="query-embedder side probe: layers of the Llama-3.2-3B shape (0 = all 28)")
@@ -848,7 +875,7 @@ def main():
     ap.add_argument("--no-cobatch", action="store_true", help="skip the co-batched side measurement (16 / 32-row decode chains): profiling "
                     "runs use it so that the kernel population is the timed region's")
     ap.add_argument("--no-side", action="store_true", help="skip the bounded passes of BASELINE configs[2..4] (side_workloads), the 100k-bank "
-                    "retrieval stress (knn_stress), the query embedder and the streaming latency probe that the default line carries")
+                    "retrieval stress (knn_stress), the query embedder and the streaming latency probe that a --full line carries")
     ap.add_argument("--workload", default="config2", choices=("config2", "config3", "config4", "config5"),
                     help="config2 (default) = BASELINE configs[1], the headline; config3 / config4 / config5 = side lines for BASELINE configs[2..4] (side_workload)")
     ap.add_argument("--force-dist", action="store_true", default=bool(os.environ.get("ASTTS_BENCH_FORCE_DIST")),
@@ -918,7 +945,7 @@ def main():
         if done is None:
             return
         for d in (done if isinstance(done, list) else [done]):
-            result["wav"] = d[2]
+            result["out"], result["wav"] = d, d[2]
             n_done[0] += 1
 
     def step():
@@ -955,6 +982,43 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        toks, mel, wav = result["out"]
+        dump_outputs(args.dump_outputs, {"knn_ids": result["ids"], "knn_scores": out_sc, "speech_tokens": toks, "mel": mel, "wav": wav})
+    total_audio = inp.audio_seconds * args.steps * world
+    pipe_depth, pipe_tuned_ms = pipe.depth, pipe.tuned_ms_per_batch
+    res = None
+    if rank == 0:
+        res = {
+            "metric": "synthesized audio sec/wall-sec (RTF^-1) + style-kNN QPS, IEMOCAP test batch",
+            "value": total_audio / dt,
+            "unit": "audio-s/wall-s",
+            "n_gpus": world,
+            "rccl_world_size": dist.get_world_size() if dist is not None else None,
+            "rccl_backend": dist.get_backend() if dist is not None else None,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f16",
+            "dtype_note": "fp16 weights / MFMA operands / KV cache, fp32 accumulation, residual stream, norms and softmax (kNN: fp16 scan + "
+                          "fp64 re-score).  Deviation: the reference's CosyVoice(model_dir) default runs fp32 (SURVEY.md 8d sanctions "
+                          "fp16 MFMA operands); parity tolerances vs the fp32 oracle are stated in tests/",
+            "data": "synthetic",
+            "config": {"workload": f"BASELINE configs[1]: batch={args.batch} utterances/GPU, kNN Q={args.batch} x N={args.bank_rows} x D={args.dim} k={args.topk}, "
+                                   f"synthesis Tt={args.text_tokens} Tp={args.prompt_tokens} Ts={args.speech_tokens} (fixed-length decode, EOS ignored) "
+                                   f"-> {inp.tm} mel frames -> {inp.tm * cfg.upsample_total} samples @ {cfg.sample_rate} Hz; CosyVoice-300M shapes, random-init weights",
+                       "parallelism": f"dp{world} (model + bank replicated, utterances sharded, all-gather of style ids only)"},
+            "pipelining": f"{pipe_depth + 2} HIP streams (front: retrieval + LM prefix / prefill + submit, {pipe_depth} decode chains, render): the LM decode chains of {pipe_depth} consecutive batches overlap flow+vocoder of the batch before them (streams chosen by PipelinedSynth.autotune during setup: {pipe_tuned_ms:.1f} ms/batch in calibration; with several ranks all keep the configuration whose slowest rank is fastest); every one of the K batches completes inside the timed region",
+        }
+    if not args.full:
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank == 0:
+            emit_json(res)
+        return
     wav_ok = bool(torch.isfinite(result["wav"]).all()) and float(result["wav"].abs().max()) <= cfg.audio_limit + 1e-6
 
     # ---- side measurement (NOT `value`): the headline's second number "including host I/O" (SURVEY.md 8d).  The same pipeline, the same
@@ -1168,7 +1232,6 @@ def main():
 
     # ---- 24 kHz side measurement (the north star's rate; the reference scripts save 22 050 Hz): same pipeline, second engine
     v24 = None
-    pipe_depth, pipe_tuned_ms = pipe.depth, pipe.tuned_ms_per_batch
     if not args.no_24khz and args.sample_rate != 24000 and args.steps >= 2:
         pipe = None
         cfg24 = SynthConfig(sample_rate=24000)
@@ -1212,38 +1275,14 @@ def main():
                 side[which] = r
             torch.cuda.empty_cache()
 
-    total_audio = inp.audio_seconds * args.steps * world
-    res = None
     if rank == 0:
-        res = {
-            "metric": "synthesized audio sec/wall-sec (RTF^-1) + style-kNN QPS, IEMOCAP test batch",
-            "value": total_audio / dt,
-            "unit": "audio-s/wall-s",
-            "n_gpus": world,
-            "rccl_world_size": dist.get_world_size() if dist is not None else None,
-            "rccl_backend": dist.get_backend() if dist is not None else None,
+        res.update({
             "gathered_ids_match_oracle": gathered_ok,
             "bank_sharded_ids_match_oracle": bank_sharded_ok,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f16",
-            "dtype_note": "fp16 weights / MFMA operands / KV cache, fp32 accumulation, residual stream, norms and softmax (kNN: fp16 scan + "
-                          "fp64 re-score).  Deviation: the reference's CosyVoice(model_dir) default runs fp32 (SURVEY.md 8d sanctions "
-                          "fp16 MFMA operands); parity tolerances vs the fp32 oracle are stated in tests/",
-            "data": "synthetic",
-            "config": {"workload": f"BASELINE configs[1]: batch={args.batch} utterances/GPU, kNN Q={args.batch} x N={args.bank_rows} x D={args.dim} k={args.topk}, "
-                                   f"synthesis Tt={args.text_tokens} Tp={args.prompt_tokens} Ts={args.speech_tokens} (fixed-length decode, EOS ignored) "
-                                   f"-> {inp.tm} mel frames -> {inp.tm * cfg.upsample_total} samples @ {cfg.sample_rate} Hz; CosyVoice-300M shapes, random-init weights",
-                       "parallelism": f"dp{world} (model + bank replicated, utterances sharded, all-gather of style ids only)"},
             "knn_qps": knn_qps,
             "knn_roofline": knn_roof,
             "ids_match_oracle": ids_ok,
             "waveform_finite_and_clamped": wav_ok,
-            "pipelining": f"{pipe_depth + 2} HIP streams (front: retrieval + LM prefix / prefill + submit, {pipe_depth} decode chains, render): the LM decode chains of {pipe_depth} consecutive batches overlap flow+vocoder of the batch before them (streams chosen by PipelinedSynth.autotune during setup: {pipe_tuned_ms:.1f} ms/batch in calibration; with several ranks all keep the configuration whose slowest rank is fastest); every one of the K batches completes inside the timed region",
             "cobatched_lm_side_measurement": ({"value": total_audio / cob["dt"], "ms_per_step": cob["ms_per_step"],
                                                "decode_chains": cob["chains"], "batches_per_chain": cob["batches_per_chain"],
                                                "rows_per_chain": cob["batches_per_chain"] * args.batch, "table_ms_per_step": cob["table_ms_per_step"],
@@ -1260,7 +1299,7 @@ def main():
             "host_io": host_io,
             "frontend_ms": host_io["frontend_ms_per_prompt"] if host_io else None,
             "side_workloads": side or None,
-        }
+        })
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0:

@@ -56,3 +56,24 @@ def test_self_launch_eight_ranks_the_node_the_north_star_names():
     res = json.loads(lines[0])
     assert res["n_gpus"] == 8 and res["rccl_world_size"] == 8 and res["ranks_seen"] == list(range(8))
     assert res["ms_per_step"] >= 15.9          # the slowest rank (rank 7 sleeps 16 ms per step) sets the time
+
+
+def test_dump_outputs_dtypes_and_seeded_sample_over_budget(tmp_path):
+    """`--dump-outputs`: floating point is written as float32, integers as float64 (exact); an array over its share of the byte
+    budget becomes the same seeded sample of its elements every time."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    ids = torch.arange(24, dtype=torch.int64).reshape(8, 3)
+    wav = torch.randn(4, 1000, generator=torch.Generator().manual_seed(0)).half()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"ids": ids, "wav": wav}, budget=2 * 2000 * 4)
+    a_ids, a_wav = np.load(tmp_path / "a" / "ids.npy"), np.load(tmp_path / "a" / "wav.npy")
+    assert a_ids.dtype == np.float64 and np.array_equal(a_ids, ids.numpy())
+    assert a_wav.dtype == np.float32 and a_wav.shape == (2000,)
+    flat = wav.float().numpy().reshape(-1)
+    assert np.isin(a_wav, flat).all()
+    assert np.array_equal(a_wav, np.load(tmp_path / "b" / "wav.npy"))

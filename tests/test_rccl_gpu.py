@@ -18,7 +18,7 @@ def test_bench_one_rank_through_rccl():
     env = dict(os.environ, ASTTS_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ASTTS_BENCH_STUB"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-24khz", "--no-side"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     # stdout is the ONE JSON line and nothing else: RCCL prints a version banner to C stdout (flushed at exit, i.e. after the
@@ -46,7 +46,7 @@ def test_bench_under_torch_distributed_run_prints_one_json_line():
     from bench import free_port
 
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-                        "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--no-24khz", "--no-cobatch", "--no-side"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -106,6 +106,41 @@ def _roofline_ok(r):
 
 
 @pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full prints the headline fields alone; --dump-outputs writes the last timed step's style ids /
+    scores, speech tokens, mel and waveform as float32 / float64 .npy files (ids equal to the oracle's for the benchmark's queries)."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import knn as oknn
+
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       env=_clean_env(), capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["unit"] == "audio-s/wall-s" and res["higher_is_better"] is True and res["dtype"] == "f16"
+    audio_per_step = 8 * 110080 / 22050
+    assert abs(res["value"] * res["ms_per_step"] / 1e3 - audio_per_step) < 1e-6 * audio_per_step
+    assert not {"knn_qps", "roofline", "ids_match_oracle", "side_workloads", "knn_stress", "cpu_baseline"} & set(res)
+    files = {p.name: np.load(p) for p in out.iterdir()}
+    assert set(files) == {"knn_ids.npy", "knn_scores.npy", "speech_tokens.npy", "mel.npy", "wav.npy"}
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    bank = bench.make_config2_bank(1000, 6144)
+    eidx, esc = oknn.knn_search(bank, bench.make_queries(bank, 8, seed=0), 3)
+    assert files["knn_ids.npy"].dtype == np.float64 and np.array_equal(files["knn_ids.npy"], eidx)
+    assert files["knn_scores.npy"].dtype == np.float32 and np.allclose(files["knn_scores.npy"], esc, atol=1e-6, rtol=0)
+    tok = files["speech_tokens.npy"]
+    assert tok.dtype == np.float64 and tok.shape == (8, 250) and np.array_equal(tok, np.round(tok)) and tok.min() >= 0
+    assert files["mel.npy"].dtype == np.float32 and files["mel.npy"].shape[0] == 8 and np.isfinite(files["mel.npy"]).all()
+    wav = files["wav.npy"]
+    assert wav.dtype == np.float32 and wav.shape == (8, 110080) and np.isfinite(wav).all() and float(np.abs(wav).max()) > 0
+
+
+@pytest.mark.gpu
 def test_bench_side_workload_as_a_line_of_its_own():
     """`python bench.py --workload config3` (BASELINE configs[2] as a line of its own): one JSON line on stdout with the default line's
     keys, `side_measurement` set, a finite waveform, its own dominant-kernel roofline and the per-kind rooflines."""
@@ -127,11 +162,11 @@ def test_bench_side_workload_as_a_line_of_its_own():
 
 @pytest.mark.gpu
 def test_default_bench_line_carries_every_baseline_config():
-    """The DEFAULT line (`python bench.py --gpus 1`, what the driver times) carries bounded passes of BASELINE configs[2..4] under
+    """The --full line (`python bench.py --gpus 1 --full`: the headline plus every side measurement) carries bounded passes of BASELINE configs[2..4] under
     `side_workloads` -- each with value, ms_per_step, its dominant kernel's roofline and per-kind rooflines -- and the 100k-bank
     retrieval stress under `knn_stress` (Q = 8 against the HBM roofline, Q = 256 against the MFMA roofline, ids checked on a sample)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-24khz",
-                        "--no-cobatch"], env=_clean_env(), capture_output=True, text=True, timeout=1500)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+                        "--no-24khz", "--no-cobatch"], env=_clean_env(), capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), r.stdout[-2000:]
