@@ -136,7 +136,8 @@ def main(args, client=None, embedder=None):
             # a rank that cannot even load its model / biographies fails its peers here instead of leaving them inside the collective
             if embedder is None:
                 from astts.cli.search_milvus import load_embedder
-                embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed)
+                embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed,
+                                         getattr(args, "base_model_path", None), getattr(args, "llm_precision", None))
             bios = load_biographies(getattr(args, "biography_json", ""))
             q, labels, failed_local = embed_rows(rows[b0:b1], embedder, bios, max_new_tokens=10, batch=getattr(args, "llm_batch", 32))
         full = np.zeros((len(rows), q.shape[1] if len(q) else 2 * embedder.cfg.hidden), np.float32)
@@ -204,8 +205,11 @@ def build_parser():
     p = argparse.ArgumentParser(description="Batch style retrieval -> JSONL hand-off")
     p.add_argument("--input_json", required=True)
     p.add_argument("--query_npy", default="", help="[rows, dim] float32 query vectors (emotion | biography halves) INSTEAD of the LLM half")
-    p.add_argument("--model_path", "--llm_dir", dest="model_path", default="", help="Llama-3.2-3B checkpoint directory (merged weights + tokenizer): "
-                   "the reference's --model_path (milvus/search_json.py:469)")
+    p.add_argument("--model_path", "--llm_dir", dest="model_path", default="", help="Llama-3.2-3B directory: a PEFT LoRA adapter (LLM.int8 + "
+                   "LoRA, as the reference) or merged weights + tokenizer: the reference's --model_path (milvus/search_json.py:469)")
+    p.add_argument("--base_model_path", default=None, help="base checkpoint directory of a LoRA adapter (local only; nothing is fetched)")
+    p.add_argument("--llm_precision", choices=("int8", "fp16"), default=None,
+                   help="embedder weights: default int8 for an adapter directory, fp16 for merged weights")
     p.add_argument("--biography_json", default="", help="{speaker: biography} (the reference samples these from the LLM; absent speakers "
                    "get its fallback text)")
     p.add_argument("--allow_random_init", action="store_true", help="run on seeded random Llama weights when model_path does not exist")

@@ -23,18 +23,22 @@ speaker_bio = {
 }
 
 
-def load_embedder(model_path, allow_random_init=False, seed=42):
+def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=None, precision=None):
     """:36-72 ``load_model_and_tokenizer``: the checkpoint directory must exist (safetensors / .bin shards + tokenizer).
-    Without one this raises unless random-init weights are explicitly allowed (plumbing runs, benchmarks)."""
+    A PEFT LoRA adapter directory (adapter_config.json: what the reference retrieves with) loads over its base checkpoint
+    (``base_model_path``, else the adapter's base_model_name_or_path as a local directory or hub-cache snapshot; never fetched) and
+    runs LLM.int8 + the unmerged LoRA branch, the reference's numerics; a merged checkpoint runs fp16.  ``precision`` ("int8" /
+    "fp16") overrides either default.  Without a directory this raises unless random-init weights are explicitly allowed
+    (plumbing runs, benchmarks)."""
     import os
 
     from astts.llm.config import LlamaShape
     from astts.llm.embedder import LlamaEmbedder
+    from astts.llm.peft import is_adapter_dir, load_peft_model
     from astts.llm.weights import load_llama_weights, make_llama_weights
 
     cfg = LlamaShape.llama32_3b()
     if model_path and os.path.isdir(model_path):
-        state = load_llama_weights(model_path)
         tok = None
         try:  # the checkpoint's own tokenizer when transformers can read it
             from transformers import AutoTokenizer
@@ -42,13 +46,22 @@ def load_embedder(model_path, allow_random_init=False, seed=42):
             tok = AutoTokenizer.from_pretrained(model_path)
         except Exception as e:  # noqa: BLE001
             print(f"Warning: no tokenizer under '{model_path}' ({e}); using the hash stand-in")
+        if is_adapter_dir(model_path):
+            if tok is not None and getattr(tok, "pad_token", None) is None and hasattr(tok, "eos_token"):
+                tok.pad_token = tok.eos_token                                   # :47-48 of the reference: pad = eos
+            state, cfg, adapter, _ = load_peft_model(model_path, base_model_path, len(tok) if tok is not None else None)
+            int8 = (precision or "int8") == "int8"
+            return LlamaEmbedder(state, cfg, tokenizer=tok, int8=int8, lora=adapter)
+        state = load_llama_weights(model_path)
+        if (precision or "fp16") == "int8":
+            return LlamaEmbedder(state, cfg, tokenizer=tok, int8=True)
         return LlamaEmbedder(state, cfg, tokenizer=tok)
     if not (allow_random_init or os.environ.get("ASTTS_ALLOW_RANDOM_INIT") == "1"):
         raise FileNotFoundError(f"no checkpoint directory at {model_path!r} (pass --allow_random_init to run on seeded random weights)")
     if os.environ.get("ASTTS_TINY_MODEL") == "1":
         cfg = LlamaShape.tiny()
     print(f"Warning: '{model_path}' not found; seeded RANDOM-INIT Llama weights at {cfg.hidden}-d (explicitly allowed)")
-    return LlamaEmbedder(make_llama_weights(cfg, seed), cfg)
+    return LlamaEmbedder(make_llama_weights(cfg, seed), cfg, int8=precision == "int8")
 
 
 def emb_text_bio(speaker, embedder):
@@ -69,7 +82,8 @@ def search_milvus(client, collection_name, embedding, top_k=3):
 
 def main(args, embedder=None):
     if embedder is None:
-        embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed)
+        embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed,
+                                 getattr(args, "base_model_path", None), getattr(args, "llm_precision", None))
     try:
         client = MilvusClient(args.db_path)
         print(f"Connected to Milvus database at '{args.db_path}'.")
@@ -117,7 +131,11 @@ def build_parser():
     parser.add_argument("--db_path", type=str, default="milvus_demo.db", help="Path to the Milvus Lite database file")
     parser.add_argument("--collection_name", type=str, default="embeddings_biographies_collection",
                         help="Name of the Milvus collection to search")
-    parser.add_argument("--model_path", type=str, default="", help="Path to the fine-tuned Llama 3.2 model (merged weights)")
+    parser.add_argument("--model_path", type=str, default="",
+                        help="Path to the fine-tuned Llama 3.2 model: a PEFT LoRA adapter directory (runs LLM.int8 + LoRA) or merged weights")
+    parser.add_argument("--base_model_path", type=str, default=None, help="base checkpoint directory of a LoRA adapter (local only)")
+    parser.add_argument("--llm_precision", choices=("int8", "fp16"), default=None,
+                        help="embedder weights: default int8 for an adapter directory, fp16 for merged weights")
     parser.add_argument("--allow_random_init", action="store_true",
                         help="run on seeded random weights when model_path does not exist (otherwise that is an error)")
     parser.add_argument("--search_text", type=str,

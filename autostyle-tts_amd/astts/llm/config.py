@@ -25,6 +25,7 @@ class LlamaShape:
     tie_embeddings: bool = True
     eos_token_id: int = 128001
     bos_token_id: int = 128000
+    eos_token_ids: tuple = ()   # further stop ids (generation_config.json's list; set by the adapter loader)
 
     @staticmethod
     def llama32_3b() -> "LlamaShape":

@@ -9,8 +9,13 @@ Replaces, in the reference's retrieval scripts (paths under /root/reference):
                                                                               src/search_milvus.py:214-221
 Every tensor operation is a HIP kernel of libastts.so (GEMMs: the MFMA family of csrc/ops_gemm.hip with fp16 activations;
 RMSNorm / RoPE / causal GQA attention at head_dim 128 / SwiGLU / mean-pool: csrc/ops_llm.hip).  fp16 weights and MFMA
-operands, fp32 residual stream, norms and softmax -- the reference itself runs the model in fp16 with 8-bit weights
-(src/search_milvus.py:47-62).  Parity: tests/test_llm_gpu.py against fixtures produced by transformers (fp32).
+operands, fp32 residual stream, norms and softmax.  Parity: tests/test_llm_gpu.py against fixtures produced by transformers (fp32).
+
+``int8=True`` runs the reference's own numerics instead (src/search_milvus.py:47-62: a PEFT LoRA adapter over LLM.int8 weights):
+the seven projections of every layer become int8 weights with per-row scales, their inputs are quantised per row with the outlier
+columns of each sequence (|x| >= ``int8_threshold``) kept in fp16 against the dequantised weight, and the adapter's LoRA branch
+(``lora``: an astts.llm.peft.LoraAdapter) runs unmerged in fp32 -- all of it csrc/ops_int8.hip (DESIGN.md "LLM.int8 + LoRA").
+No fp16 copy of those projections is kept.  A ``lora`` without ``int8`` is merged into the fp16 weights at load.
 
 The tokenizer is the checkpoint's own (tokenizer.json: not available offline); anything with ``encode(text) -> list[int]``
 plugs in (`transformers.AutoTokenizer` when the checkpoint directory is given).  ``HashTokenizer`` is a labelled
@@ -61,7 +66,8 @@ class HashTokenizer:
 
 
 class LlamaEmbedder:
-    def __init__(self, state: dict, cfg: LlamaShape, device=None, tokenizer=None, max_length: int = 512):
+    def __init__(self, state: dict, cfg: LlamaShape, device=None, tokenizer=None, max_length: int = 512, int8: bool = False, lora=None,
+                 int8_threshold: float = 6.0):
         if not torch.cuda.is_available():
             raise RuntimeError("astts.llm needs a ROCm GPU; there is no CPU fallback in the product path")
         if cfg.head_dim != 128:
@@ -72,6 +78,9 @@ class LlamaEmbedder:
         self.max_length = max_length                                  # truncation=True, max_length=512: src/search_milvus.py:92
         import os
         self.mfma_attention = os.environ.get("ASTTS_LLM_ATTN", "mfma") != "valu"
+        self.int8, self.int8_threshold = bool(int8), float(int8_threshold)
+        if lora is not None and not self.int8:
+            state = _merge_lora(state, lora)
         dev = self.device
         with torch.cuda.device(dev):
             f = lambda k: state[k].to(device=dev, dtype=torch.float32).contiguous()
@@ -79,6 +88,9 @@ class LlamaEmbedder:
             self.L = []
             for i in range(cfg.layers):
                 p = f"model.layers.{i}."
+                if self.int8:
+                    self.L.append(self._int8_layer(state, i, lora, dev))
+                    continue
                 wqkv = torch.cat([state[p + "self_attn.q_proj.weight"], state[p + "self_attn.k_proj.weight"],
                                   state[p + "self_attn.v_proj.weight"]], 0)
                 wgu = torch.cat([state[p + "mlp.gate_proj.weight"], state[p + "mlp.up_proj.weight"]], 0)
@@ -90,6 +102,35 @@ class LlamaEmbedder:
             self.head = PackedWeight(head, None, dev)
             self._rope_lock = threading.Lock()
             self._rope_tables(max(max_length, 16) + 64)
+
+    def _int8_layer(self, state: dict, i: int, lora, dev) -> dict:
+        p = f"model.layers.{i}."
+        pairs = {} if lora is None else lora.pairs
+        scaling = 1.0 if lora is None else lora.scaling
+
+        def w(*names):
+            parts = []
+            for nm in names:
+                ab = pairs.get((i, nm.split(".")[-1]))
+                parts.append((state[p + nm + ".weight"], None if ab is None else ab[0], None if ab is None else ab[1]))
+            if any(q[1] is not None for q in parts):          # a fused projection with LoRA on some parts: zero pairs on the others
+                r = next(q[1].shape[0] for q in parts if q[1] is not None)
+                parts = [q if q[1] is not None else (q[0], torch.zeros(r, q[0].shape[1]), torch.zeros(q[0].shape[0], r)) for q in parts]
+            return ops.Int8Weight(parts, scaling, dev)
+
+        f = lambda k: state[k].to(device=dev, dtype=torch.float32).contiguous()
+        return {"n1": f(p + "input_layernorm.weight"), "n2": f(p + "post_attention_layernorm.weight"),
+                "wqkv": w("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "wo": w("self_attn.o_proj"),
+                "wgu": w("mlp.gate_proj", "mlp.up_proj"), "wd": w("mlp.down_proj")}
+
+    def _lin(self, x: torch.Tensor, w, seg, residual=None, out_dtype=torch.float32) -> torch.Tensor:
+        """One projection: the fp16 GEMM (ops.linear), or with int8 the LLM.int8 + LoRA GEMM on the segments ``seg`` = (ids, count)."""
+        if self.int8:
+            return w(x, seg[0], seg[1], self.int8_threshold, residual=residual, out_dtype=out_dtype)
+        return ops.linear(x, w, residual=residual, out_dtype=out_dtype)
+
+    def _is_eos(self, tok: int) -> bool:
+        return tok == self.cfg.eos_token_id or tok in self.cfg.eos_token_ids
 
     def _rope_tables(self, n: int) -> None:
         """(cos, sin) rows for positions < n, published as ONE tuple: a thread that sees the new cos also sees the new sin."""
@@ -117,18 +158,24 @@ class LlamaEmbedder:
         cos, sin = self._rope           # one consistent pair for the whole pass
         hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
         x = ops.embedding(self.embed, ids.to(self.device))
+        seg = None
+        if self.int8:                  # LLM.int8 segments: one per text; the right padding belongs to none
+            sid = torch.arange(b, dtype=torch.int32, device=self.device)[:, None].expand(b, t)
+            if lens is not None:
+                sid = torch.where(torch.arange(t, device=self.device)[None, :] < lens.to(self.device)[:, None], sid, -1)
+            seg = (sid.reshape(-1).to(torch.int32).contiguous(), b)
         for L in self.L:
             h = ops.rmsnorm(x, L["n1"], cfg.rms_eps)                              # fp16: its only consumer is an MFMA operand
-            qkv = ops.linear(h, L["wqkv"], out_dtype=torch.float16)              # [B, T, hq + 2 hk]
+            qkv = self._lin(h, L["wqkv"], seg, out_dtype=torch.float16)          # [B, T, hq + 2 hk]
             ops.rope_llama_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)             # q heads then k heads: contiguous
             if self.mfma_attention:                                                # v_mfma_f32_32x32x16_f16 (csrc/ops_llm.hip attn_gqa_mfma)
                 a = ops.attn_gqa(qkv[..., :hq], qkv[..., hq:hq + hk], qkv[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens=lens)
             else:                                                                  # the VALU kernel: the second implementation (tests)
                 a = ops.attn_causal_gqa(qkv[..., :hq], qkv[..., hq:hq + hk], qkv[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens)
-            x = ops.linear(a, L["wo"], residual=x)
+            x = self._lin(a, L["wo"], seg, residual=x)
             h = ops.rmsnorm(x, L["n2"], cfg.rms_eps)
-            gu = ops.linear(h, L["wgu"], out_dtype=torch.float16)
-            x = ops.linear(ops.swiglu(gu), L["wd"], residual=x)
+            gu = self._lin(h, L["wgu"], seg, out_dtype=torch.float16)
+            x = self._lin(ops.swiglu(gu), L["wd"], seg, residual=x)
         return ops.rmsnorm(x, self.norm, cfg.rms_eps, out_dtype=torch.float32)
 
     def embed_ids(self, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -149,7 +196,7 @@ class LlamaEmbedder:
             lg = self.logits_last(torch.tensor([out], dtype=torch.int64, device=self.device))
             nxt = int(torch.argmax(lg[0]))                                        # one scalar back to the host per token
             out.append(nxt)
-            if nxt == self.cfg.eos_token_id:
+            if self._is_eos(nxt):
                 break
         return out
 
@@ -180,21 +227,28 @@ class LlamaEmbedder:
         start = torch.tensor([t - n for n in lens], dtype=torch.int32, device=dev)
         cache = [torch.empty((t_max, b, 2 * hk), dtype=torch.float16, device=dev) for _ in self.L]
         toks = torch.zeros((n_new, b), dtype=torch.int32, device=dev)
+        seg_prefill = seg_step = None
+        if self.int8:                  # LLM.int8 segments: a prompt's tokens in the prefill (left padding: none), one row per decode step
+            bi = torch.arange(b, dtype=torch.int32, device=dev)
+            seg_prefill = (torch.where(torch.arange(t, dtype=torch.int32, device=dev)[:, None] >= start[None, :], bi[None, :], -1)
+                           .reshape(-1).to(torch.int32).contiguous(), b)
+            seg_step = (bi, b)
 
         def stack(x: torch.Tensor, pos0: int) -> torch.Tensor:
             """x fp32 [T', B, hidden] = the new positions pos0 .. pos0 + T' - 1 -> final-norm hidden of the LAST of them [B, hidden]."""
             tn = x.shape[0]
+            seg = seg_prefill if pos0 == 0 else seg_step
             for L, kv in zip(self.L, cache):
                 h = ops.rmsnorm(x, L["n1"], cfg.rms_eps)
-                qkv = ops.linear(h, L["wqkv"], out_dtype=torch.float16)                       # [T', B, hq + 2 hk]
+                qkv = self._lin(h, L["wqkv"], seg, out_dtype=torch.float16)                   # [T', B, hq + 2 hk]
                 ops.rope_llama_ex_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim, pos0=pos0, shift=start, time_major=True)
                 kv[pos0:pos0 + tn].copy_(qkv[..., hq:])                                        # K (rotated) | V into the cache rows
                 a = ops.attn_gqa(qkv[..., :hq], kv[:pos0 + tn, :, :hk], kv[:pos0 + tn, :, hk:], cfg.heads, cfg.kv_heads, cfg.head_dim,
                                  key_start=start, pos0=pos0, time_major=True)
-                x = ops.linear(a, L["wo"], residual=x)
+                x = self._lin(a, L["wo"], seg, residual=x)
                 h = ops.rmsnorm(x, L["n2"], cfg.rms_eps)
-                gu = ops.linear(h, L["wgu"], out_dtype=torch.float16)
-                x = ops.linear(ops.swiglu(gu), L["wd"], residual=x)
+                gu = self._lin(h, L["wgu"], seg, out_dtype=torch.float16)
+                x = self._lin(ops.swiglu(gu), L["wd"], seg, residual=x)
             return ops.rmsnorm(x[-1].contiguous(), self.norm, cfg.rms_eps, out_dtype=torch.float32)
 
         x = ops.embedding(self.embed, ids.to(dev))
@@ -209,7 +263,7 @@ class LlamaEmbedder:
             row = list(p)
             for s in range(n_new):
                 row.append(int(got[s, j]))
-                if row[-1] == cfg.eos_token_id:
+                if self._is_eos(row[-1]):
                     break
             out.append(row)
         return out
@@ -275,3 +329,14 @@ Answer:"""
         """milvus/search_json.py:201-229 / src/search_milvus.py:214-221: [emotion | biography] float32, un-normalised."""
         e = self.get_embeddings([emotion_text, biography_text])
         return np.concatenate((e[0], e[1])).astype(np.float32)
+
+
+def _merge_lora(state: dict, lora) -> dict:
+    """W + scaling * B A in fp32 for the fp16 path (the int8 path keeps the branch unmerged, as peft does)."""
+    from .peft import PROJ
+
+    out = dict(state)
+    for (i, p), (a, b) in lora.pairs.items():
+        k = f"model.layers.{i}.{PROJ[p]}.weight"
+        out[k] = state[k].float() + lora.scaling * (b.float() @ a.float())
+    return out

@@ -905,3 +905,142 @@ def mean_pool(x: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Ten
     out = torch.empty((b, c), dtype=torch.float32, device=x.device)
     _lib.check(_L().astts_op_mean_pool(x.data_ptr(), _p(lens), out.data_ptr(), b, t, c, _st()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- LLM.int8 + LoRA (csrc/ops_int8.hip)
+_I8_SIGS = {
+    "astts_op_i8_quant_weight": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "astts_op_i8_quant_act_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "astts_op_i8_quant_act": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "astts_op_i8_lora_down": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "astts_op_i8_gemm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                   c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_int64,
+                                   c_void_p, c_int32, c_int64, c_void_p]),
+}
+_SIGS.update(_I8_SIGS)
+_lib.register_signatures(_I8_SIGS)
+
+I8_OUT_F32, I8_OUT_F16, I8_OUT_ACC = range(3)
+
+
+def i8_quantize_weight(w: torch.Tensor, device=None):
+    """fp32 / fp16 ``[n, k]`` -> (CB int8 ``[n_pad, k_pad]``, SCB fp32 ``[n_pad]``): astts_op_i8_quant_weight (cast to fp16 first)."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    n, k = (int(s) for s in w.shape)
+    src = w.to(device=device, dtype=torch.float16 if w.dtype == torch.float16 else torch.float32).contiguous()
+    n_pad, k_pad = _up(n, 128), _up(k, 128)
+    cb = torch.empty((n_pad, k_pad), dtype=torch.int8, device=device)
+    scb = torch.empty((n_pad,), dtype=torch.float32, device=device)
+    _lib.check(_L().astts_op_i8_quant_weight(src.data_ptr(), 1 if src.dtype == torch.float16 else 0, cb.data_ptr(), scb.data_ptr(),
+                                             n, k, n_pad, k_pad, _st()))
+    return cb, scb
+
+
+class I8Act:
+    """The quantised activations of one call (astts_op_i8_quant_act): ``ca`` int8 ``[m, k_pad]``, ``sca`` fp32 ``[m]``, ``xo`` fp16
+    ``[m, k_pad]`` (the first ``count`` columns meaningful), ``cols`` int32 ``[k_pad]`` and ``cnt`` int32 ``[1]`` -- on the device."""
+
+    def __init__(self, ca, sca, xo, cols, cnt, k):
+        self.ca, self.sca, self.xo, self.cols, self.cnt, self.k = ca, sca, xo, cols, cnt, k
+
+
+def i8_quantize_act(x: torch.Tensor, seg: torch.Tensor, segments: int, tau: float) -> I8Act:
+    """x fp16 ``[m, k]`` (row stride free), seg int32 ``[m]`` (segment of each row, -1: pad) -> I8Act.  No host synchronisation."""
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1, (x.dtype, x.shape, x.stride())
+    assert seg.dtype == torch.int32 and seg.is_contiguous() and seg.numel() == x.shape[0] and seg.device == x.device
+    m, k = (int(s) for s in x.shape)
+    k_pad, dev = _up(k, 128), x.device
+    ca = torch.empty((m, k_pad), dtype=torch.int8, device=dev)
+    sca = torch.empty((m,), dtype=torch.float32, device=dev)
+    xo = torch.empty((m, k_pad), dtype=torch.float16, device=dev)
+    cols = torch.empty((k_pad,), dtype=torch.int32, device=dev)
+    cnt = torch.empty((1,), dtype=torch.int32, device=dev)
+    segments = max(int(segments), 1)
+    wsb = int(_L().astts_op_i8_quant_act_workspace_bytes(segments, k)) if tau > 0 else 0
+    ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
+    _lib.check(_L().astts_op_i8_quant_act(x.data_ptr(), x.stride(0), seg.data_ptr(), m, k, k_pad, segments, float(tau), ca.data_ptr(),
+                                          sca.data_ptr(), xo.data_ptr(), k_pad, cols.data_ptr(), cnt.data_ptr(), ws.data_ptr(), wsb, _st()))
+    return I8Act(ca, sca, xo, cols, cnt, k)
+
+
+def i8_lora_down(x: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """x fp16 ``[m, k]``, a fp32 ``[r_tot, k]`` (r_tot % 32 == 0) -> fp32 ``[m, r_tot]`` = x . a^T (astts_op_i8_lora_down)."""
+    assert x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    a = _f32(a)
+    m, k = (int(s) for s in x.shape)
+    assert a.shape[1] == k and a.shape[0] % 32 == 0, (a.shape, k)
+    t = torch.empty((m, a.shape[0]), dtype=torch.float32, device=x.device)
+    _lib.check(_L().astts_op_i8_lora_down(x.data_ptr(), x.stride(0), a.data_ptr(), m, k, a.shape[0], t.data_ptr(), a.shape[0], _st()))
+    return t
+
+
+def i8_gemm(act: I8Act, cb: torch.Tensor, scb: torch.Tensor, n: int, outliers: bool = True, t: Optional[torch.Tensor] = None,
+            lora_b: Optional[torch.Tensor] = None, r: int = 0, groups=(0, 0), scaling: float = 1.0,
+            residual: Optional[torch.Tensor] = None, out_kind: int = I8_OUT_F32) -> torch.Tensor:
+    """astts_op_i8_gemm on quantised activations: -> ``[m, n]`` fp32 / fp16 / int32 (``out_kind``)."""
+    m, k_pad = act.ca.shape
+    assert cb.shape[1] == k_pad and cb.shape[0] >= _up(n, 128) and scb.numel() >= cb.shape[0]
+    dt = {I8_OUT_F32: torch.float32, I8_OUT_F16: torch.float16, I8_OUT_ACC: torch.int32}[out_kind]
+    out = torch.empty((m, n), dtype=dt, device=act.ca.device)
+    ldr = 0
+    if residual is not None:
+        residual = _f32(residual).reshape(m, n)
+        ldr = n
+    if r > 0:
+        assert t is not None and lora_b is not None and lora_b.shape[1] == r and lora_b.shape[0] >= cb.shape[0]
+        t, lora_b = _f32(t), _f32(lora_b)
+    g1, g2 = groups
+    _lib.check(_L().astts_op_i8_gemm(act.ca.data_ptr(), act.sca.data_ptr(), cb.data_ptr(), scb.data_ptr(), m, n, k_pad,
+                                     act.xo.data_ptr() if outliers else None, act.xo.shape[1], act.cols.data_ptr(), act.cnt.data_ptr(),
+                                     _p(t) if r > 0 else None, t.shape[1] if r > 0 else 0, _p(lora_b) if r > 0 else None, r, g1, g2,
+                                     float(scaling), _p(residual), ldr, out.data_ptr(), out_kind, n, _st()))
+    return out
+
+
+class Int8Weight:
+    """One quantised projection (LLM.int8) with its LoRA branch, in the layout astts_op_i8_gemm reads.  ``parts``: the fused weights'
+    pieces ``[(w [n_i, k], lora_a [r, k] or None, lora_b [n_i, r] or None), ...]`` (q | k | v, gate | up), at most three; every
+    piece but the last has a multiple of 32 rows.  No fp16 copy of the weight is kept."""
+
+    def __init__(self, parts, scaling: float = 1.0, device=None):
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        assert 1 <= len(parts) <= 3
+        w = torch.cat([p[0].to(torch.float32) for p in parts], 0) if len(parts) > 1 else parts[0][0]
+        self.n, self.k = (int(s) for s in w.shape)
+        self.cb, self.scb = i8_quantize_weight(w, device)
+        self.k_pad = self.cb.shape[1]
+        bounds, acc = [], 0
+        for p in parts[:-1]:
+            acc += int(p[0].shape[0])
+            bounds.append(acc)
+        assert all(b % 32 == 0 for b in bounds), f"Int8Weight: fused parts must split at multiples of 32 rows, got {bounds}"
+        big = 1 << 30
+        self.groups = (bounds + [big, big])[:2] if bounds else (big, big)
+        self.scaling = float(scaling)
+        has = [p[1] is not None for p in parts]
+        assert all(has) or not any(has), "Int8Weight: LoRA on some parts of a fused projection only is not supported"
+        self.r = 0
+        if any(has):
+            r = int(parts[0][1].shape[0])
+            assert all(int(p[1].shape[0]) == r and tuple(p[2].shape) == (p[0].shape[0], r) for p in parts)
+            r8 = _up(r, 8)
+            r_tot = _up(len(parts) * r8, 32)
+            a = torch.zeros((r_tot, self.k), dtype=torch.float32)
+            for g, p in enumerate(parts):
+                a[g * r8:g * r8 + r] = p[1].to(torch.float32)
+            b = torch.zeros((self.cb.shape[0], r8), dtype=torch.float32)
+            b[:self.n, :r] = torch.cat([p[2].to(torch.float32) for p in parts], 0)
+            self.lora_a = a.to(device).contiguous()
+            self.lora_b = b.to(device).contiguous()
+            self.r = r8
+
+    def __call__(self, x: torch.Tensor, seg: torch.Tensor, segments: int, tau: float, residual=None, out_dtype=torch.float32):
+        """x fp16 ``[..., k]`` -> ``[..., n]``: the int8 GEMM, its outlier columns and the LoRA branch (``residual`` fp32 added)."""
+        x2 = x.reshape(-1, self.k)
+        act = i8_quantize_act(x2, seg, segments, tau)
+        t = i8_lora_down(x2, self.lora_a) if self.r else None
+        y = i8_gemm(act, self.cb, self.scb, self.n, outliers=tau > 0, t=t, lora_b=self.lora_b if self.r else None, r=self.r,
+                    groups=self.groups, scaling=self.scaling, residual=residual,
+                    out_kind=I8_OUT_F16 if out_dtype == torch.float16 else I8_OUT_F32)
+        return y.view(*x.shape[:-1], self.n)

@@ -465,6 +465,36 @@ int astts_op_swiglu(const void* gate_up_f16, void* out_f16, int64_t rows, int32_
 /* out[b, c] = mean over the first lens[b] (NULL: t) tokens of x fp32 [b, t, c] */
 int astts_op_mean_pool(const float* x, const int32_t* lens, float* out, int32_t b, int32_t t, int32_t c, astts_stream_t stream);
 
+/* LLM.int8 linear layers with an unmerged LoRA branch (csrc/ops_int8.hip; DESIGN.md "LLM.int8 + LoRA"): bitsandbytes' Linear8bitLt
+ * at inference (threshold tau) under peft's LoRA layer, for the embedder's q/k/v/o/gate/up/down projections.
+ * Weight, once: SCB[n] = max |fp16(W[n, :])|, CB = rint(fp16(W) * (127 / SCB)) -> int8 [n_pad, k_pad] (k_pad % 128 == 0, n_pad % 128
+ * == 0, zero padded), SCB fp32 [n_pad].  w is fp32 (w_f16 == 0) or fp16 [n, k]. */
+int astts_op_i8_quant_weight(const void* w, int32_t w_f16, int8_t* cb, float* scb, int32_t n, int32_t k, int32_t n_pad, int32_t k_pad,
+                             astts_stream_t stream);
+/* Activations, every call: x fp16 [m, ldx]; seg int32 [m] = the row's segment (one sequence) in [0, segments), -1 = pad row.
+ * Outlier columns of a segment: the columns where some row of it has |x| >= tau (tau <= 0: none).  SCA fp32 [m] = max |x| over the
+ * row's elements below tau; CA int8 [m, k_pad] = 0 on its segment's outlier columns, else rint(x * (127 / SCA)).  cols int32
+ * [>= k_pad] = the union's columns ascending, padded with 0 to a multiple of 8; *cnt (device) = their number; xo fp16 [m, ldo >= k_pad]
+ * = x at cols[j] where that column is the row's segment's, else 0.  Nothing synchronises with the host.  workspace: at least
+ * astts_op_i8_quant_act_workspace_bytes(segments, k) bytes (unused when tau <= 0). */
+size_t astts_op_i8_quant_act_workspace_bytes(int32_t segments, int32_t k);
+int astts_op_i8_quant_act(const void* x_f16, int64_t ldx, const int32_t* seg, int32_t m, int32_t k, int32_t k_pad, int32_t segments,
+                          float tau, int8_t* ca, float* sca, void* xo_f16, int32_t ldo, int32_t* cols, int32_t* cnt, void* workspace,
+                          size_t workspace_bytes, astts_stream_t stream);
+/* LoRA down-projection t fp32 [m, ldt] = x fp16 [m, ldx] . a^T, a fp32 [r_tot, k] (r_tot % 32 == 0), fp32 products and sums */
+int astts_op_i8_lora_down(const void* x_f16, int64_t ldx, const float* a, int32_t m, int32_t k, int32_t r_tot, float* t, int32_t ldt,
+                          astts_stream_t stream);
+/* out[m, n] = acc * SCA[m] * SCB[n] / 127^2  (acc = sum_k CA . CB, exact int32, v_mfma_i32_32x32x32_i8)
+ *           + sum_{j < *cnt} xo[m, j] * (CB[n, cols[j]] * SCB[n] / 127)          (xo == NULL: no outlier term)
+ *           + scaling * sum_{i < r} t[m, g(n) * r + i] * lora_b[n, i]            (r == 0: no LoRA term; g(n) = (n >= g1) + (n >= g2),
+ *                                                                                  g1, g2 multiples of 32: the parts of a fused weight)
+ *           + residual[m, n] (fp32, or NULL).  out_kind 0: fp32, 1: fp16, 2: the raw int32 accumulator.  lora_b fp32 [n_pad, r],
+ * r % 8 == 0.  CB / SCB as astts_op_i8_quant_weight made them (n_pad >= n rounded up to 128). */
+int astts_op_i8_gemm(const int8_t* ca, const float* sca, const int8_t* cb, const float* scb, int32_t m, int32_t n, int32_t k_pad,
+                     const void* xo_f16, int32_t ldo, const int32_t* cols, const int32_t* cnt, const float* t, int32_t ldt,
+                     const float* lora_b, int32_t r, int32_t g1, int32_t g2, float scaling, const float* residual, int64_t ldr,
+                     void* out, int32_t out_kind, int64_t ldc, astts_stream_t stream);
+
 /* LayerNorm (scale / shift folded into the weights by the caller) + q|k|v projection + masked multi-head attention of one
  * transformer block of the flow estimator in one launch (csrc/ops_tfm_fused.hip): x fp32 [b, t, c] -> out fp16
  * [b, t, heads*64].  wqkv_frag: the q | k | v weight [3*heads*64, c] re-ordered by astts_op_tfm_pack_frag (from the row-major
