@@ -29,6 +29,7 @@ _SIGS = {
                                       c_void_p] + [c_int32] * 11 + [c_float, c_float, c_void_p, c_size_t, c_void_p]),
     "astts_op_gemm_fused_workspace_bytes": (c_size_t, []),
     "astts_op_gemm_set_ring_mode": (c_int32, [c_int32]),
+    "astts_op_gemm_kernel_kind": (c_int32, [c_int64] + [c_int32] * 8),
     "astts_op_gemm_ln": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64,
                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "astts_op_attn_relpos_ex": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
@@ -331,6 +332,20 @@ def set_gemm_ring_mode(mode: int) -> None:
     """-1 auto (default), 0 ring kernel off, 1 / 2 / 3 / 4 / 5 force the 128x128 / 128x64 / 64x64 / 256x256 one-barrier / 256x256
     eight-phase ring tile (tests, tuning)."""
     _lib.check(_L().astts_op_gemm_set_ring_mode(int(mode)))
+
+
+GEMM_KINDS = ("skinny", "ring", "T32", "T128", "T128x64", "T64k128", "T64k64")     # ASTTS_GEMM_KIND_*
+
+
+def gemm_kernel_kind(m: int, n: int, cin: int, taps: int = 1, plain: bool = True, x_f16: bool = False, out_f16: bool = False,
+                     x_aligned: bool = True) -> str:
+    """The kernel ``gemm`` runs for this shape, as the launcher itself decides it (astts_op_gemm_kernel_kind: a host query, no GPU
+    call).  ``plain``: one tap, stride 1, no padding, ``t_out == t_in``, no ``in_lens``.  -> one of GEMM_KINDS."""
+    kind = _L().astts_op_gemm_kernel_kind(m, n, cin, _up(cin, 64), taps, 1 if plain else 0, 1 if x_f16 else 0, 1 if out_f16 else 0,
+                                          1 if x_aligned else 0)
+    if kind < 0:
+        _lib.check(kind)
+    return GEMM_KINDS[kind]
 
 
 def linear(x: torch.Tensor, w: PackedWeight, act: str = "none", residual=None, alpha: float = 1.0,

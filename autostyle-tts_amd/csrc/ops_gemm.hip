@@ -1472,9 +1472,37 @@ static void launch_tile(const GemmArgs& a, hipStream_t st) {
 
 static int g_ring_mode_override = -1;   // -1: rule below / ASTTS_GEMM_RING; 0: ring kernel off; 1..3: force that tile
 
+// the ring switch in force: astts_op_gemm_set_ring_mode (tests) over the environment's ASTTS_GEMM_RING over the rule (-1)
+static int ring_mode_in_force() {
+    static const int ring_env0 = [] { const char* e = getenv("ASTTS_GEMM_RING"); return e ? atoi(e) : -1; }();
+    return g_ring_mode_override >= 0 ? g_ring_mode_override : ring_env0;
+}
+
+// Which kernel family serves a contraction (ASTTS_GEMM_KIND_*): the ONE place that decides it.  launch_gemm switches on the answer and
+// astts_op_gemm_kernel_kind exports it, so a test that wants a given tile asks the rule the launcher runs and not a copy of it.
+// plain: taps == 1, stride == 1, pad == 0, t_in == t_out, no row lengths; x_aligned: fp16 x at a 16-byte aligned address with lda % 8 == 0
+// (the LDS-DMA staging of the ring kernels); ring_mode: ring_mode_in_force() (0 switches the ring kernels off).
+static int gemm_kernel_kind(int64_t m, int n, int cin, int cin_pad, int taps, bool plain, bool x_f16, bool out_f16, bool x_aligned,
+                            int ring_mode) {
+    if (m <= 32 && plain && !x_f16 && !out_f16) return ASTTS_GEMM_KIND_SKINNY;
+    // fp16 activations, plain GEMM, whole 64-wide K tiles: the LDS-DMA ring kernel
+    if (plain && x_f16 && cin == cin_pad && x_aligned && m >= 64 && n > 32 && ring_mode != 0) return ASTTS_GEMM_KIND_RING;
+    auto blocks = [&](int bm, int bn) { return cdiv(m, bm) * cdiv(n, bn); };
+    const int64_t want = 384;  // >= 1.5 blocks per CU
+    // K tile: cin_pad is a multiple of 64, so 64 never straddles a tap; 128 needs cin_pad % 128 == 0
+    const bool k128 = (cin_pad % 128) == 0 && taps * cin_pad >= 256;
+    if (n <= 32) return ASTTS_GEMM_KIND_T32;
+    if (n > 64 && blocks(128, 128) >= want) return ASTTS_GEMM_KIND_T128;   // measured: the 128x128 tile is fastest at BK=32 (2+ blocks/CU, small K)
+    if (blocks(128, 64) >= want) return ASTTS_GEMM_KIND_T128X64;
+    return k128 ? ASTTS_GEMM_KIND_T64K128 : ASTTS_GEMM_KIND_T64K64;
+}
+
 static int launch_gemm(const GemmArgs& a, hipStream_t st) {
     const bool plain = a.taps == 1 && a.stride == 1 && a.pad == 0 && a.t_in == a.t_out && !a.in_lens;   // (row lengths: the tile kernel masks them)
-    if (a.m <= 32 && plain && !a.x_f16 && !a.out_f16) {
+    const int ring_env = ring_mode_in_force();
+    const int kind = gemm_kernel_kind(a.m, a.n, a.cin, a.cin_pad, a.taps, plain, a.x_f16 != 0, a.out_f16 != 0,
+                                      (a.lda & 7) == 0 && ((uintptr_t)a.x & 15) == 0, ring_env);
+    if (kind == ASTTS_GEMM_KIND_SKINNY) {
         // the block keeps its m rows of x as an fp16 image in LDS: rows are taken in chunks that fit 160 KB
         // (only m > 16 with K > 2048 needs two passes, e.g. the FFN-out projection of a 32-row decode group)
         // split-K (a.sk_part given): deep, narrow GEMMs (the FFN-out projection: K = 4096 onto 1024 columns = 64 column
@@ -1529,11 +1557,7 @@ static int launch_gemm(const GemmArgs& a, hipStream_t st) {
                   "astts_op_gemm_fused: gather / LayerNorm / split output need m <= 32 and a plain (non-conv) GEMM");
     const bool prof = prof_begin(ASTTS_PROF_GEMM_TILE, st, 2.0 * (double)a.m * a.n * a.cin * a.taps);
     auto blocks = [&](int bm, int bn) { return cdiv(a.m, bm) * cdiv(a.n, bn); };
-    // fp16 activations, plain GEMM, whole 64-wide K tiles: the LDS-DMA ring kernel
-    static const int ring_env0 = [] { const char* e = getenv("ASTTS_GEMM_RING"); return e ? atoi(e) : -1; }();
-    const int ring_env = g_ring_mode_override >= 0 ? g_ring_mode_override : ring_env0;   // astts_op_gemm_set_ring_mode (tests)
-    if (plain && a.x_f16 && a.cin == a.cin_pad && (a.lda & 7) == 0 && ((uintptr_t)a.x & 15) == 0 && a.m >= 64 && a.n > 32 &&
-        ring_env != 0) {
+    if (kind == ASTTS_GEMM_KIND_RING) {
         static bool ring_attr = false;
         if (!ring_attr) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring<2, 2, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
@@ -1601,19 +1625,12 @@ static int launch_gemm(const GemmArgs& a, hipStream_t st) {
         set_error("gemm_scan: the block-maximum epilogue needs the ring kernels");
         return ASTTS_ERR_INVALID;
     }
-    const int64_t want = 384;  // >= 1.5 blocks per CU
-    // K tile: cin_pad is a multiple of 64, so 64 never straddles a tap; 128 needs cin_pad % 128 == 0
-    const bool k128 = (a.cin_pad % 128) == 0 && a.taps * a.cin_pad >= 256;
-    if (a.n <= 32) {
-        launch_tile<4, 1, 1, 1, 64>(a, st);
-    } else if (a.n > 64 && blocks(128, 128) >= want) {
-        launch_tile<2, 2, 2, 2, 32>(a, st);   // measured: the 128x128 tile is fastest at BK=32 (2+ blocks/CU, small K)
-    } else if (blocks(128, 64) >= want) {
-        launch_tile<2, 2, 2, 1, 32>(a, st);
-    } else if (k128) {
-        launch_tile<2, 2, 1, 1, 128>(a, st);
-    } else {
-        launch_tile<2, 2, 1, 1, 64>(a, st);
+    switch (kind) {
+        case ASTTS_GEMM_KIND_T32: launch_tile<4, 1, 1, 1, 64>(a, st); break;
+        case ASTTS_GEMM_KIND_T128: launch_tile<2, 2, 2, 2, 32>(a, st); break;
+        case ASTTS_GEMM_KIND_T128X64: launch_tile<2, 2, 2, 1, 32>(a, st); break;
+        case ASTTS_GEMM_KIND_T64K128: launch_tile<2, 2, 1, 1, 128>(a, st); break;
+        default: launch_tile<2, 2, 1, 1, 64>(a, st); break;
     }
     if (prof) prof_end(ASTTS_PROF_GEMM_TILE, st);
     ASTTS_CHECK_LAUNCH();
@@ -1668,6 +1685,13 @@ int astts_op_gemm_set_ring_mode(int32_t mode) {
     ASTTS_REQUIRE(mode >= -1 && mode <= 5, ASTTS_ERR_INVALID, "astts_op_gemm_set_ring_mode: mode=%d (-1 auto, 0 off, 1..5 tile)", mode);
     g_ring_mode_override = mode;
     return ASTTS_OK;
+}
+
+int astts_op_gemm_kernel_kind(int64_t m, int32_t n, int32_t cin, int32_t cin_pad, int32_t taps, int32_t plain, int32_t x_f16,
+                              int32_t out_f16, int32_t x_aligned) {
+    ASTTS_REQUIRE(m >= 1 && n >= 1 && cin >= 1 && taps >= 1 && cin_pad >= cin && cin_pad % 64 == 0, ASTTS_ERR_INVALID,
+                  "astts_op_gemm_kernel_kind: bad shape m=%lld n=%d cin=%d cin_pad=%d taps=%d", (long long)m, n, cin, cin_pad, taps);
+    return gemm_kernel_kind(m, n, cin, cin_pad, taps, plain != 0, x_f16 != 0, out_f16 != 0, x_aligned != 0, ring_mode_in_force());
 }
 
 int astts_op_pack_weight(const float* src, void* dst_f16, int32_t n, int32_t taps, int32_t cin,

@@ -212,6 +212,23 @@ int astts_op_gemm_fused(const float* x, const int32_t* gather, const float* ln_g
  * embedder's projections, the kNN scan of >= 64 queries; results bit-identical to 4).  Process-global
  * test / tuning switch: the parity tests run the benchmark's projection shapes through every tile. */
 int astts_op_gemm_set_ring_mode(int32_t mode);
+/* Which kernel astts_op_gemm / _ex / _lens runs for a shape: a pure host query (no stream, no GPU call) of the rule the launcher itself
+ * switches on, so that a test can assert the tile it means to exercise.  plain != 0: taps == 1, stride == 1, pad == 0, t_in == t_out and
+ * no in_lens; x_aligned != 0: fp16 x at a 16-byte aligned address with lda % 8 == 0 (what the ring kernels' LDS-DMA staging needs; not
+ * looked at otherwise).  Honours astts_op_gemm_set_ring_mode / ASTTS_GEMM_RING (0: never RING).  -> ASTTS_GEMM_KIND_* or ASTTS_ERR_INVALID.
+ *   SKINNY   m <= 32, plain, fp32 in and out (gemm_skinny16)      RING     plain fp16 GEMM on whole 64-wide K tiles, m >= 64, n > 32
+ *   T32      128 x 32 tile (n <= 32)                              T128     128 x 128, BK 32: n > 64 and >= 384 such tiles
+ *   T128X64  128 x 64, BK 32: >= 384 such tiles                   T64K128  64 x 64, BK 128: cin_pad % 128 == 0, taps * cin_pad >= 256
+ *   T64K64   64 x 64, BK 64: everything else */
+#define ASTTS_GEMM_KIND_SKINNY 0
+#define ASTTS_GEMM_KIND_RING 1
+#define ASTTS_GEMM_KIND_T32 2
+#define ASTTS_GEMM_KIND_T128 3
+#define ASTTS_GEMM_KIND_T128X64 4
+#define ASTTS_GEMM_KIND_T64K128 5
+#define ASTTS_GEMM_KIND_T64K64 6
+int astts_op_gemm_kernel_kind(int64_t m, int32_t n, int32_t cin, int32_t cin_pad, int32_t taps, int32_t plain, int32_t x_f16,
+                              int32_t out_f16, int32_t x_aligned);
 int astts_op_gemm_ln(const void* x_f16, const void* w_f16, const float* bias, const float* residual, float* out,
                      const float* ln_gamma, const float* ln_beta, float ln_eps, void* ln_out_f16, int64_t m, int32_t n, int32_t cin,
                      int32_t cin_pad, int32_t lda, int32_t ldc, int32_t ldr, int32_t ld_ln, astts_stream_t stream);

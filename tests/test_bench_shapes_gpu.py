@@ -131,6 +131,56 @@ def test_fullshape_estimator_pass_config2_geometry():
         assert err < 5e-3
 
 
+def test_hift_vocoder_benchmark_length_matches_oracle():
+    """The vocoder at production widths and at the benchmark's length against the oracle: B = 2 utterances of Tm = 430 mel frames
+    (BASELINE config 2: 250 speech tokens -> 110 080 samples), same source signal as the oracle's own.  At this size the second
+    transposed convolution has m = 2 * 3441 = 6882 rows onto 1024 columns = 54 * 8 = 432 tiles of 128 x 128, i.e. the 128 x 128
+    implicit-GEMM tile that serves the benchmark (asserted through the launcher's own rule); the oracle tests at 9 and 16 frames stay
+    on the 64 x 64 tiles.  Bars as in test_hift_vocoder_production_widths_match_oracle (tests/test_synth_gpu.py).  Measured: waveform
+    error 1.8e-4 of full scale (bar 5e-3), SNR 64.7 dB (bar 40); the oracle takes 0.9 s on 16 threads, the test 1.2 s."""
+    import time
+
+    from astts import ops
+    from astts.synth.config import SynthConfig
+    from astts.synth.model import HiftVocoder
+    from astts.synth.weights import make_hift_weights
+    from oracle import synth as osyn
+
+    TOL_WAV = 5e-3       # vocoder waveform, absolute on a 0.99 full scale (tests/test_synth_gpu.py)
+    cfg = SynthConfig()
+    sd = make_hift_weights(cfg, 3)
+    g = torch.Generator().manual_seed(34)
+    b, tm = 2, 430
+    assert tm * cfg.upsample_total == 110080
+    # the two transposed convolutions of this call, as the launcher sees them: [b, t, c] -> m = b * (t + 1) rows, n = stride * c / 2 columns
+    t1 = tm
+    c1 = cfg.hift_base
+    for i, s in enumerate(cfg.up_rates):
+        kind = ops.gemm_kernel_kind(b * (t1 + 1), s * (c1 // 2), c1, taps=2, plain=False)
+        print(f"conv-transpose {i}: m = {b * (t1 + 1)}, n = {s * (c1 // 2)}, cin = {c1} -> {kind}")
+        if i == 1:
+            assert (b * (t1 + 1), s * (c1 // 2)) == (6882, 1024) and kind == "T128"
+        t1, c1 = t1 * s, c1 // 2
+    mel = torch.randn(b, tm, cfg.mel, generator=g)
+    nh = cfg.nb_harmonics + 1
+    phase0 = (torch.rand(b, nh, generator=g) * 2 - 1) * math.pi
+    phase0[:, 0] = 0
+    noise = torch.randn(b, tm * cfg.upsample_total, nh, generator=g)
+    voc = HiftVocoder(sd, cfg, torch.device(DEV))
+    t0 = time.perf_counter()
+    f0_ref = osyn.hift_f0(sd, cfg, mel)
+    src_ref = osyn.hift_source(sd, cfg, f0_ref, phase0, noise)
+    wav_ref = osyn.hift_decode(sd, cfg, mel, src_ref)
+    print(f"oracle vocoder (B={b}, Tm={tm}): {time.perf_counter() - t0:.1f} s on {torch.get_num_threads()} threads")
+    wav = voc.decode(mel.to(DEV), src_ref.to(DEV)).cpu()
+    assert wav.shape == wav_ref.shape == (b, tm * cfg.upsample_total)
+    err = float((wav - wav_ref).abs().max())
+    snr = float(10 * torch.log10(wav_ref.double().pow(2).sum() / (wav_ref.double() - wav.double()).pow(2).sum().clamp_min(1e-30)))
+    print(f"benchmark-length vocoder (B={b}, Tm={tm}): abs err vs oracle {err:.2e} (tol {TOL_WAV:.0e}), SNR {snr:.1f} dB (> 40)")
+    assert err < TOL_WAV
+    assert snr > 40.0 and float(wav.abs().max()) <= cfg.audio_limit + 1e-6
+
+
 def test_config3_longform_batch_rows_are_batch_independent():
     """BASELINE config 3 at full size: 64 rows x (Tt=64 text tokens, Ts=250 speech tokens) in ONE engine call.  The LM
     decodes 64 rows as two 32-row groups on two streams, flow + vocoder take the 64-row batch: rows 32..63 must equal
