@@ -1,7 +1,8 @@
 """Batch retrieval -> JSONL hand-off file: /root/reference/milvus/search_json.py (:313-461) on one GPU in one command.
 
-    python -m astts.cli.search_json --input_json in.jsonl --model_path /path/to/llama-3.2-3b [--biography_json bios.json] \
-        --db_path milvus_demo.db --output_file search_results.json [--file_prefix_path /data/seg_wav]
+    python -m astts.cli.search_json --input_json in.jsonl --model_path /path/to/llama-3.2-3b [--generate_biographies] \
+        [--biography_json bios.json] [--biography_out bios.json] --db_path milvus_demo.db --output_file search_results.json \
+        [--file_prefix_path /data/seg_wav]
 
 Per input row {zh_text, speaker} (:382-461): emotion label (greedy continuation of the few-shot prompt, :154-198) -> combined
 embedding [label | speaker biography] through the Llama embedder (mean-pooled last hidden state, :76-109, :201-229) -> top-1 COSINE
@@ -11,9 +12,13 @@ come from ONE KV-cached greedy decode (``LlamaEmbedder.generate_emotion_labels``
 embedded once each in padded batches, and all queries of the file go to the retrieval kernel as ONE batch (the reference loops
 rows one by one, re-embedding the same six labels and the same biography every time).
 
-Speaker biographies: the reference SAMPLES them from the LLM (:113-151, do_sample=True, 250 tokens: not reproducible, and outside
-the hot path -- SURVEY.md 2 #9); here they come from ``--biography_json`` ({speaker: biography}, e.g. the output of the reference's
-own bank construction) and fall back to the reference's own fallback text "This is a placeholder biography." (:375, :400).
+Speaker biographies: the reference SAMPLES them from the LLM, one per speaker, from the speaker's utterances joined with "\n"
+(:113-151, :326, :369-378: do_sample=True, temperature 0.7, top_p 0.9, 250 tokens).  ``--generate_biographies`` does the same here
+(``LlamaEmbedder.generate_biographies``: ``--llm_batch`` speakers per KV-cached decode, every token drawn on the GPU by
+astts_op_sample_topk_topp, ``--max_new_tokens`` as the reference's flag; repeatable: the draws are keyed by ``--seed`` and the speaker's
+place in the file).  ``--biography_json`` ({speaker: biography}) supplies biographies from a file instead; its entries win over
+generated ones.  ``--biography_out`` writes the map that was used, in the form ``--biography_json`` reads back.  A speaker with neither
+(or whose generation fails) gets the reference's fallback text "This is a placeholder biography." (:375-378, :400).
 
 ``--query_npy q.npy`` ([rows, dim] float32) replaces the LLM half with precomputed query vectors, one per input row.
 
@@ -63,6 +68,44 @@ def load_biographies(path):
     if isinstance(data, dict):
         return {str(k): str(v) for k, v in data.items()}
     return {str(d["speaker"]): str(d["biography"]) for d in data if "speaker" in d and "biography" in d}
+
+
+def speaker_conversations(rows):
+    """milvus/search_json.py:293-311, :370: {speaker: its non-empty zh_text joined with "\n"}, speakers in order of first appearance."""
+    texts = {}
+    for r in rows:
+        t = r.get("zh_text", "").strip()
+        if t:
+            texts.setdefault(r.get("speaker", "UNKNOWN_SPEAKER"), []).append(t)
+    return {s: "\n".join(t) for s, t in texts.items()}
+
+
+def generate_speaker_biographies(conversations, embedder, max_new_tokens=250, batch=32, seed=0):
+    """milvus/search_json.py:367-378 for {speaker: conversation}: one sampled biography per speaker, ``batch`` speakers per decode.
+    The speakers of a decode that raises get the placeholder text (:375-378); nothing is run again on the device after a failure."""
+    speakers = list(conversations)
+    out = {}
+    for c0 in range(0, len(speakers), max(batch, 1)):
+        chunk = speakers[c0:c0 + max(batch, 1)]
+        try:
+            bios = embedder.generate_biographies([(conversations[s], s) for s in chunk], max_new_tokens, seed, batch=len(chunk), first_index=c0)
+            for s in chunk:
+                print(f"Generated biography for speaker '{s}'.")
+        except Exception as e:  # noqa: BLE001
+            print(f"Error generating biography for speaker(s) {chunk}: {e}")
+            traceback.print_exc()
+            bios = [PLACEHOLDER_BIOGRAPHY] * len(chunk)
+        out.update(zip(chunk, bios))
+    return out
+
+
+def write_biographies(path, biographies):
+    """The {speaker: biography} map as ``load_biographies`` reads it back."""
+    out_dir = os.path.dirname(path)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    with open(path, "w", encoding="utf-8") as f:
+        json.dump(biographies, f, ensure_ascii=False, indent=2)
 
 
 def embed_rows(rows, embedder, biographies, max_new_tokens=10, batch=32):
@@ -132,13 +175,27 @@ def main(args, client=None, embedder=None):
         # the LLM half (:372-411) for THIS rank's rows only: the full-size query array is filled in the rank's shard and nowhere
         # else (sharded_search reads exactly that slice; no query vector crosses GPUs)
         b0, b1, _ = parallel.shard_bounds(len(rows), world, rank)
-        with parallel.rank_work(dist, "search_json: load the embedder, emotion label + embedding"):     # agreed before the search's all-gather:
-            # a rank that cannot even load its model / biographies fails its peers here instead of leaving them inside the collective
+        # every block below is work a rank does alone; rank_work agrees on failure at its end, so a rank that cannot load its model /
+        # biographies fails its peers there instead of leaving them inside the next collective
+        with parallel.rank_work(dist, "search_json: load the embedder and the biographies"):
             if embedder is None:
                 from astts.cli.search_milvus import load_embedder
                 embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed,
                                          getattr(args, "base_model_path", None), getattr(args, "llm_precision", None))
             bios = load_biographies(getattr(args, "biography_json", ""))
+        if getattr(args, "generate_biographies", False):
+            # rank 0 samples the biographies of the speakers the file does not cover (all rows' speakers, not its shard's) and every
+            # rank receives the map: the queries, and so the output file, are the one-process run's
+            gen = None
+            with parallel.rank_work(dist, "search_json: generate the biographies"):
+                if rank == 0:
+                    conv = {s: c for s, c in speaker_conversations(rows).items() if s not in bios}
+                    gen = generate_speaker_biographies(conv, embedder, getattr(args, "max_new_tokens", 250), getattr(args, "llm_batch", 32),
+                                                       args.seed)
+            bios = {**parallel.broadcast_object(gen, dist), **bios}
+        with parallel.rank_work(dist, "search_json: emotion label + embedding"):
+            if getattr(args, "biography_out", "") and rank == 0:
+                write_biographies(args.biography_out, bios)
             q, labels, failed_local = embed_rows(rows[b0:b1], embedder, bios, max_new_tokens=10, batch=getattr(args, "llm_batch", 32))
         full = np.zeros((len(rows), q.shape[1] if len(q) else 2 * embedder.cfg.hidden), np.float32)
         full[b0:b1] = q
@@ -212,6 +269,10 @@ def build_parser():
                    help="embedder weights: default int8 for an adapter directory, fp16 for merged weights")
     p.add_argument("--biography_json", default="", help="{speaker: biography} (the reference samples these from the LLM; absent speakers "
                    "get its fallback text)")
+    p.add_argument("--generate_biographies", action="store_true", help="sample each speaker's biography from the LLM, as the reference does "
+                   "(milvus/search_json.py:367-378); entries of --biography_json win")
+    p.add_argument("--max_new_tokens", type=int, default=250, help="tokens per generated biography (the reference's flag)")
+    p.add_argument("--biography_out", default="", help="write the {speaker: biography} map that was used (the file --biography_json reads)")
     p.add_argument("--allow_random_init", action="store_true", help="run on seeded random Llama weights when model_path does not exist")
     p.add_argument("--llm_batch", type=int, default=32, help="rows per batched greedy decode / embedding pass")
     p.add_argument("--seed", type=int, default=42)

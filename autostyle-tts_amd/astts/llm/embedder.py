@@ -208,12 +208,19 @@ class LlamaEmbedder:
         Layout: prompts are LEFT-padded to a common length, time-major ``[T, B]`` (the rows of a step are contiguous in the cache
         ``[T_max, B, 2 * kv_heads * 128]`` per layer); ``key_start[b]`` masks a row's pad keys and shifts its RoPE positions so that its
         first token has position 0, as in the one-at-a-time reference run."""
+        return self._generate_batch(prompts, max_new_tokens, lambda s, lg, out: ops.argmax_rows(lg, out=out))
+
+    def _generate_batch(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, pick, keep_logits: bool = False, poll: int = 0):
+        """The KV-cached decode both continuations share: ``pick(step, logits fp32 [B, vocab], out int32 [B])`` chooses each step's
+        tokens on the device.  ``keep_logits``: also return every step's logits ``[max_new_tokens, B, vocab]`` (device).  ``poll`` > 0:
+        every ``poll`` steps one scalar comes back to ask whether every row has produced an EOS (then the loop stops: what a row holds
+        after its first EOS is cut off below either way, so no returned token changes)."""
         cfg, dev = self.cfg, self.device
         prompts = [[int(i) for i in p] for p in prompts]
         b, lens = len(prompts), [len(p) for p in prompts]
         t, n_new = max(lens), int(max_new_tokens)
         if n_new <= 0:
-            return [list(p) for p in prompts]
+            return ([list(p) for p in prompts], torch.empty((0, b, cfg.vocab), device=dev)) if keep_logits else [list(p) for p in prompts]
         t_max = t + n_new
         if t_max > self._rope[0].shape[0]:
             with self._rope_lock:
@@ -251,11 +258,18 @@ class LlamaEmbedder:
                 x = self._lin(ops.swiglu(gu), L["wd"], seg, residual=x)
             return ops.rmsnorm(x[-1].contiguous(), self.norm, cfg.rms_eps, out_dtype=torch.float32)
 
+        logits = torch.empty((n_new, b, cfg.vocab), dtype=torch.float32, device=dev) if keep_logits else None
+        eos = torch.tensor(sorted({int(cfg.eos_token_id), *(int(e) for e in cfg.eos_token_ids)}), dtype=torch.int32, device=dev) if poll > 0 else None
         x = ops.embedding(self.embed, ids.to(dev))
         for s in range(n_new):
             h_last = stack(x, 0 if s == 0 else t + s - 1)
-            ops.argmax_rows(ops.linear(h_last, self.head), out=toks[s])
+            lg = ops.linear(h_last, self.head)
+            pick(s, lg, toks[s])
+            if keep_logits:
+                logits[s].copy_(lg)
             if s + 1 < n_new:
+                if poll > 0 and (s + 1) % poll == 0 and bool(torch.isin(toks[:s + 1], eos).any(0).all()):
+                    break
                 x = ops.embedding(self.embed, toks[s])[None]
         got = toks.cpu().numpy()                                                               # the one synchronisation
         out = []
@@ -266,7 +280,33 @@ class LlamaEmbedder:
                 if self._is_eos(row[-1]):
                     break
             out.append(row)
-        return out
+        return (out, logits) if keep_logits else out
+
+    @staticmethod
+    def row_uniforms(seed: int, index: int, n: int) -> torch.Tensor:
+        """The ``n`` uniforms of the row that is number ``index`` in the caller's list: its own generator, so that a row's draws do
+        not depend on which other rows share its batch."""
+        g = torch.Generator().manual_seed((int(seed) & 0xffffffff) * 1000003 + int(index))
+        return torch.rand(n, generator=g, dtype=torch.float32)
+
+    def generate_sample_batch(self, prompts: Sequence[Sequence[int]], max_new_tokens: int = 250, temperature: float = 0.7, top_k: int = 50,
+                              top_p: float = 0.9, uniforms: Optional[torch.Tensor] = None, seed: int = 0, return_logits: bool = False):
+        """do_sample=True continuation (milvus/search_json.py:139-147: model.generate(do_sample=True, temperature=0.7, top_p=0.9,
+        max_new_tokens=250); top_k=50 is GenerationConfig's default, which that call inherits) of several prompts at once: the decode of
+        ``generate_greedy_batch`` with each step's token drawn on the device by ``astts_op_sample_topk_topp`` (temperature -> top-k ->
+        top-p -> inverse-CDF draw on an injected uniform; definition: include/astts.h).  ``uniforms``: fp32 ``[max_new_tokens, B]`` in
+        [0, 1); absent, row j's column is ``row_uniforms(seed, j, max_new_tokens)``.  One copy back at the end (plus one scalar every
+        32 steps to stop once every row has ended); rows are cut at their first EOS.  ``return_logits`` (tests, small vocabularies):
+        returns ``(rows, logits fp32 [max_new_tokens, B, vocab])`` and runs every step."""
+        b, n_new = len(prompts), int(max_new_tokens)
+        if uniforms is None:
+            uniforms = torch.stack([self.row_uniforms(seed, j, max(n_new, 0)) for j in range(b)], 1) if b else torch.empty((max(n_new, 0), 0))
+        uniforms = torch.as_tensor(uniforms, dtype=torch.float32)
+        if tuple(uniforms.shape) != (max(n_new, 0), b):
+            raise ValueError(f"uniforms {tuple(uniforms.shape)}: expected [max_new_tokens, B] = {(max(n_new, 0), b)}")
+        u = uniforms.to(self.device).contiguous()
+        pick = lambda s, lg, out: ops.sample_topk_topp(lg, u[s], temperature, top_k, top_p, out=out)
+        return self._generate_batch(prompts, n_new, pick, keep_logits=return_logits, poll=0 if return_logits else 32)
 
     def generate_greedy(self, ids: Sequence[int], max_new_tokens: int = 10) -> List[int]:
         """do_sample=False continuation of one prompt (milvus/search_json.py:178-188): the cached path with one row."""
@@ -311,6 +351,35 @@ Answer:"""
         outs = self.generate_greedy_batch(prompts, max_new_tokens)
         dec = (lambda o: self.tokenizer.decode(o, skip_special_tokens=True)) if self._decode_takes_skip else self.tokenizer.decode   # search_json.py:191
         return [dec(o).strip().lower() for o in outs]
+
+    BIOGRAPHY_PROMPT = """
+Given this conversation between speakers:
+"
+{}
+"
+In overall of above conversation, what do you think about the characteristics of speaker {}? (Note: provide an answer within 250 words)
+"""
+
+    def generate_biography(self, full_conversation: str, speaker_name: str, max_new_tokens: int = 250, seed: int = 0) -> str:
+        """milvus/search_json.py:113-151: the sampled continuation of the biography prompt, decoded without special tokens, the prompt
+        removed, stripped."""
+        return self.generate_biographies([(full_conversation, speaker_name)], max_new_tokens, seed)[0]
+
+    def generate_biographies(self, items: Sequence, max_new_tokens: int = 250, seed: int = 0, batch: int = 32, first_index: int = 0) -> List[str]:
+        """The biographies of several (conversation, speaker) pairs, ``batch`` prompts per sampled decode.  Pair number i draws from
+        ``row_uniforms(seed, first_index + i, ...)`` whatever batch it lands in (``first_index``: the pairs are a slice of a longer list)."""
+        items = [(str(c), str(s)) for c, s in items]
+        texts = [self.BIOGRAPHY_PROMPT.format(c, s) for c, s in items]
+        prompts = [list(self.tokenizer.encode(t)) for t in texts]                                  # untruncated, as tokenizer(prompting) there
+        dec = (lambda o: self.tokenizer.decode(o, skip_special_tokens=True)) if self._decode_takes_skip else self.tokenizer.decode
+        out: List[str] = []
+        n_new = int(max_new_tokens)
+        for c0 in range(0, len(items), max(int(batch), 1)):
+            idx = range(c0, min(c0 + max(int(batch), 1), len(items)))
+            u = torch.stack([self.row_uniforms(seed, first_index + i, max(n_new, 0)) for i in idx], 1)
+            rows = self.generate_sample_batch([prompts[i] for i in idx], n_new, uniforms=u)
+            out.extend(dec(r).replace(texts[i], "").strip() for i, r in zip(idx, rows))       # :148-150
+        return out
 
     @property
     def _decode_takes_skip(self) -> bool:

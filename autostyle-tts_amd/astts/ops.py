@@ -170,6 +170,7 @@ _SIGS.update({   # query-embedder operators (csrc/ops_llm.hip)
     "astts_op_attn_gqa": (c_int32, [c_void_p] * 6 + [c_int32] * 7 + [c_int64] * 6 + [c_float, c_void_p]),
     "astts_op_rope_llama_ex": (c_int32, [c_void_p] * 4 + [c_int32] * 7 + [c_void_p]),
     "astts_op_argmax_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
+    "astts_op_sample_topk_topp": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),
 })
 _lib.register_signatures(_SIGS)
 
@@ -902,6 +903,21 @@ def argmax_rows(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     if out is None:
         out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
     _lib.check(_L().astts_op_argmax_rows(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _st()))
+    return out
+
+
+def sample_topk_topp(logits: torch.Tensor, uniforms: torch.Tensor, temperature: float, top_k: int, top_p: float,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 ``[rows, vocab]`` (row stride >= vocab) + fp32 uniforms ``[rows]`` in [0, 1) -> int32 ``[rows]``: one token per row by
+    temperature -> top-k -> top-p -> inverse-CDF draw (definition: include/astts.h), on the device: the sampled step's token."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1, (logits.dtype, logits.shape)
+    uniforms = _f32(uniforms)
+    assert uniforms.shape == (logits.shape[0],), uniforms.shape
+    if out is None:
+        out = torch.empty((logits.shape[0],), dtype=torch.int32, device=logits.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.shape == (logits.shape[0],)
+    _lib.check(_L().astts_op_sample_topk_topp(logits.data_ptr(), logits.stride(0), uniforms.data_ptr(), out.data_ptr(), logits.shape[0],
+                                              logits.shape[1], float(temperature), int(top_k), float(top_p), _st()))
     return out
 
 

@@ -477,6 +477,20 @@ int astts_op_rope_llama_ex(void* x_f16, const float* cos_tab, const float* sin_t
                            int32_t heads, int32_t ld, int32_t head_dim, int32_t pos0, astts_stream_t stream);
 /* out[row] = argmax over x[row, 0 .. n) (ties: the lowest index, as torch.argmax): the greedy step's token, on the device */
 int astts_op_argmax_rows(const float* x, int32_t* out, int32_t rows, int32_t n, int64_t ld, astts_stream_t stream);
+/* The sampled step of model.generate(do_sample=True, temperature, top_k, top_p) on the device (csrc/ops_sample.hip): transformers'
+ * TemperatureLogitsWarper -> TopKLogitsWarper -> TopPLogitsWarper -> multinomial, the draw in closed form on an injected uniform.
+ * logits fp32 [rows, ld >= vocab], uniforms fp32 [rows] in [0, 1), out_tokens int32 [rows].  Per row:
+ *   1. candidates = the top_k (vocab if smaller) largest logits under the total order (logit descending, token id ascending);
+ *   2. s = logit / temperature (fp32), p = softmax(s) over the candidates only;
+ *   3. nucleus = the candidates, in that order, whose EXCLUSIVE prefix sum of p is < top_p (the first candidate always);
+ *      top_p = 1 keeps every candidate, whatever the fp32 prefix sum rounds to);
+ *   4. q = p / sum(p over the nucleus); token = the first nucleus entry whose inclusive prefix sum of q exceeds u (the last entry
+ *      if rounding leaves none).
+ * temperature > 0, 0 < top_p <= 1, 1 <= top_k <= 1024 (ASTTS_ERR_RANGE otherwise).  Two deviations from transformers: top_k = 0
+ * ("off") is not supported, and transformers keeps EVERY entry tied with the k-th value where this keeps exactly top_k (the two differ
+ * only on an exact fp32 tie at the k-th place).  Bit-for-bit repeatable: integer histograms, fixed-order sums. */
+int astts_op_sample_topk_topp(const float* logits, int64_t ld, const float* uniforms, int32_t* out_tokens, int32_t rows, int32_t vocab,
+                              float temperature, int32_t top_k, float top_p, astts_stream_t stream);
 /* out = silu(gate) * up on a fused projection gate_up fp16 [rows, ldg] = gate[f] | up[f] */
 int astts_op_swiglu(const void* gate_up_f16, void* out_f16, int64_t rows, int32_t f, int32_t ldg, int32_t ldo, astts_stream_t stream);
 /* out[b, c] = mean over the first lens[b] (NULL: t) tokens of x fp32 [b, t, c] */
