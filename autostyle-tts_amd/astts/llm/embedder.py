@@ -56,10 +56,11 @@ class HashTokenizer:
     def __init__(self, cfg: LlamaShape):
         self.cfg = cfg
 
-    def encode(self, text: str) -> List[int]:
+    def encode(self, text: str, add_special_tokens: bool = True) -> List[int]:
         import zlib
 
-        return [self.cfg.bos_token_id] + [3 + zlib.crc32(w.encode("utf-8")) % (self.cfg.vocab - 3) for w in text.split()]
+        return ([self.cfg.bos_token_id] if add_special_tokens else []) + [3 + zlib.crc32(w.encode("utf-8")) % (self.cfg.vocab - 3)
+                                                                          for w in text.split()]
 
     def decode(self, ids: Sequence[int]) -> str:
         return " ".join(f"<{int(i)}>" for i in ids)
@@ -311,6 +312,108 @@ class LlamaEmbedder:
     def generate_greedy(self, ids: Sequence[int], max_new_tokens: int = 10) -> List[int]:
         """do_sample=False continuation of one prompt (milvus/search_json.py:178-188): the cached path with one row."""
         return self.generate_greedy_batch([ids], max_new_tokens)[0]
+
+    # ------------------------------------------------------------------ scoring: log-probabilities of given tokens
+    def token_logprobs(self, ids: torch.Tensor, lens: Optional[torch.Tensor] = None, start: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ids int ``[B, T]`` (right-padded), lens int ``[B]`` or None -> fp32 ``[B, T - 1]`` on the GPU: entry ``[b, t]`` is the
+        log-probability of token ``t + 1`` given the tokens ``<= t`` of row b, for every real position (``t + 1 < lens[b]``); padding
+        -- and, with ``start`` (int ``[B]``), every target position before ``start[b]`` -- is 0 and never reaches the head.
+        One pass of the decoder stack (``hidden``: fp16, or int8 + LoRA, as constructed), then the rows that have a target are gathered
+        and scored by ``ops.head_logprob``: the head GEMM with a log-sum-exp epilogue, no ``[rows, vocab]`` logits."""
+        b, t = ids.shape
+        out = torch.zeros((b, max(t - 1, 0)), dtype=torch.float32, device=self.device)
+        if t < 2:
+            return out
+        ids = ids.to(self.device)
+        if lens is not None:
+            lens = lens.to(device=self.device, dtype=torch.int32)
+        h = self.hidden(ids, lens)                                                # fp32 [B, T, hidden]
+        pos = torch.arange(1, t, device=self.device)[None, :]                     # the target's position in the sequence
+        take = torch.ones((b, t - 1), dtype=torch.bool, device=self.device) if lens is None else pos < lens[:, None]
+        if start is not None:
+            take = take & (pos >= start.to(self.device)[:, None])
+        rb, rt = torch.nonzero(take, as_tuple=True)
+        if rb.numel() == 0:
+            return out
+        rows = h[rb, rt].to(torch.float16)                                        # the GEMM's operand type (ops.linear converts the same way)
+        targets = ids[rb, rt + 1].to(torch.int32)
+        out[rb, rt] = ops.head_logprob(rows, self.head, targets)
+        return out
+
+    def _pad_batch(self, seqs: Sequence[Sequence[int]]):
+        tmax = max(len(s) for s in seqs)
+        ids = torch.zeros((len(seqs), tmax), dtype=torch.int64)
+        for i, s in enumerate(seqs):
+            ids[i, : len(s)] = torch.tensor(list(s), dtype=torch.int64)
+        return ids, torch.tensor([len(s) for s in seqs], dtype=torch.int32)
+
+    def _ids_of(self, x, continuation: bool = False) -> List[int]:
+        """Token ids of a text (or the ids themselves).  Tokenizer protocol: ``encode(text) -> ids`` (with whatever special tokens
+        the model expects in front) for prompts; a CONTINUATION carries no special tokens of its own, so a continuation given as
+        text needs ``encode(text, add_special_tokens=False)`` (transformers' signature; HashTokenizer has it).  A tokenizer without
+        that keyword cannot say what it adds: pass the continuation as token ids then."""
+        if not isinstance(x, str):
+            return [int(i) for i in x]
+        if not continuation:
+            return [int(i) for i in self.tokenizer.encode(x)]
+        import inspect
+        try:
+            ps = inspect.signature(self.tokenizer.encode).parameters
+            plain = "add_special_tokens" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
+        except (TypeError, ValueError):
+            plain = True
+        if not plain:
+            raise TypeError("score / classify: this tokenizer's encode() has no add_special_tokens keyword, so a continuation given as "
+                            "text cannot be tokenised without its special tokens; pass token ids")
+        return [int(i) for i in self.tokenizer.encode(x, add_special_tokens=False)]
+
+    def score(self, prompts: Sequence, continuations: Sequence, batch: int = 32):
+        """Per (prompt, continuation) pair: ``(logprobs, total)`` -- the log-probability of every continuation token given the prompt
+        and the continuation before it (a list of floats), and their sum.  Texts go through the tokenizer (the continuation without
+        special tokens), sequences of ints are taken as token ids.  ONE teacher-forced pass over prompt + continuation per pair,
+        ``batch`` pairs at a time (right-padded); only the continuation's positions are scored."""
+        if len(prompts) != len(continuations):
+            raise ValueError("score: one continuation per prompt")
+        pairs = [(self._ids_of(p), self._ids_of(c, continuation=True)) for p, c in zip(prompts, continuations)]
+        for p, c in pairs:
+            if not p or not c:
+                raise ValueError("score: a pair needs at least one prompt token (the context of the first scored token) and one continuation token")
+        res = []
+        step = max(int(batch), 1)
+        for c0 in range(0, len(pairs), step):
+            chunk = pairs[c0:c0 + step]
+            ids, lens = self._pad_batch([p + c for p, c in chunk])
+            start = torch.tensor([len(p) for p, _ in chunk], dtype=torch.int32)
+            lp = self.token_logprobs(ids, lens, start=start).cpu()
+            for i, (p, c) in enumerate(chunk):
+                row = lp[i, len(p) - 1: len(p) - 1 + len(c)]
+                res.append(([float(v) for v in row], float(row.sum(dtype=torch.float64))))
+        return res
+
+    def perplexity(self, texts: Sequence, batch: int = 32) -> float:
+        """exp(mean negative log-likelihood) over every scored token of ``texts`` (each token after a text's first)."""
+        seqs = [self._ids_of(t) for t in texts]
+        total, count = 0.0, 0
+        step = max(int(batch), 1)
+        for c0 in range(0, len(seqs), step):
+            ids, lens = self._pad_batch(seqs[c0:c0 + step])
+            total += float(self.token_logprobs(ids, lens).sum(dtype=torch.float64))
+            count += int((lens - 1).clamp(min=0).sum())
+        if count == 0:
+            raise ValueError("perplexity: no text has a second token to score")
+        return math.exp(-total / count)
+
+    def classify(self, prompts: Sequence, labels: Sequence, batch: int = 32):
+        """Closed-set choice: for each prompt the label whose tokens have the largest SUMMED log-probability after it -- the sum
+        decides (it is the log-probability of the label as a whole; the per-token mean favours long labels and is returned for
+        inspection only); ties go to the first label.  -> ``(choice, sums, means)``: a list of label indices and two float64 numpy
+        arrays ``[prompts, labels]``.  The prompt is replayed once per label (``len(labels)`` rows per prompt in the batch)."""
+        p_ids = [self._ids_of(p) for p in prompts]
+        l_ids = [self._ids_of(l, continuation=True) for l in labels]
+        flat = self.score([p for p in p_ids for _ in l_ids], [l for _ in p_ids for l in l_ids], batch=batch)
+        sums = np.array([s for _, s in flat], dtype=np.float64).reshape(len(p_ids), len(l_ids))
+        means = sums / np.array([len(l) for l in l_ids], dtype=np.float64)[None, :]
+        return [int(i) for i in sums.argmax(axis=1)], sums, means
 
     # ------------------------------------------------------------------ the reference's call surface
     def _encode(self, text: str) -> List[int]:

@@ -172,6 +172,11 @@ _SIGS.update({   # query-embedder operators (csrc/ops_llm.hip)
     "astts_op_argmax_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
     "astts_op_sample_topk_topp": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),
 })
+_SIGS.update({   # token log-probabilities under the LM head without a logits plane (csrc/ops_score.hip)
+    "astts_op_head_logprob_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "astts_op_head_logprob": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+})
 _lib.register_signatures(_SIGS)
 
 ACT = {"none": 0, "relu": 1, "silu": 2, "swish": 2, "gelu": 3, "mish": 4, "elu": 5, "tanh": 6, "leaky": 7}
@@ -919,6 +924,33 @@ def sample_topk_topp(logits: torch.Tensor, uniforms: torch.Tensor, temperature: 
     _lib.check(_L().astts_op_sample_topk_topp(logits.data_ptr(), logits.stride(0), uniforms.data_ptr(), out.data_ptr(), logits.shape[0],
                                               logits.shape[1], float(temperature), int(top_k), float(top_p), _st()))
     return out
+
+
+def head_logprob(h: torch.Tensor, head: PackedWeight, targets: torch.Tensor, want_lse: bool = False, want_argmax: bool = False,
+                 vocab: Optional[int] = None):
+    """Log-probability of ``targets`` under the LM head, with no ``[rows, vocab]`` logits plane (astts_op_head_logprob: the head GEMM's
+    epilogue keeps a (max, sum-exp) pair per 256 columns, a second kernel merges them in a fixed order).
+
+    ``h``: fp16 ``[rows, hidden]`` final-norm hidden states (row stride a multiple of 8, unit column stride); ``targets``: int32
+    ``[rows]``, -1 = ignore (that row's log-probability is 0); ``vocab``: the columns that count (default: all of the head's).
+    -> fp32 ``[rows]``, or a tuple ``(logprob[, lse][, argmax])`` with the log-sum-exp (fp32) and the largest logit's column (int32,
+    ties: the lowest) when asked for.  Bit-for-bit repeatable; a row's result does not depend on the other rows."""
+    assert h.is_cuda and h.dtype == torch.float16 and h.dim() == 2 and h.shape[1] == head.cin and h.stride(1) == 1, (h.dtype, h.shape, h.stride())
+    rows = h.shape[0]
+    assert targets.is_cuda and targets.dtype == torch.int32 and targets.shape == (rows,) and targets.is_contiguous(), (targets.dtype, targets.shape)
+    vocab = head.n if vocab is None else int(vocab)
+    out = torch.empty((rows,), dtype=torch.float32, device=h.device)
+    lse = torch.empty((rows,), dtype=torch.float32, device=h.device) if want_lse else None
+    am = torch.empty((rows,), dtype=torch.int32, device=h.device) if want_argmax else None
+    if rows == 0:
+        res = (out,) + ((lse,) if want_lse else ()) + ((am,) if want_argmax else ())
+        return res[0] if len(res) == 1 else res
+    ws = torch.empty((int(_L().astts_op_head_logprob_workspace_bytes(rows, vocab)),), dtype=torch.uint8, device=h.device)
+    w = Weight(head.data.data_ptr(), _p(head.bias), head.n, head.cin, head.cin_pad, head.taps)
+    _lib.check(_L().astts_op_head_logprob(h.data_ptr(), h.stride(0), ctypes.byref(w), targets.data_ptr(), rows, vocab, out.data_ptr(),
+                                          _p(lse), _p(am), None, ws.data_ptr(), ws.numel(), _st()))
+    res = (out,) + ((lse,) if want_lse else ()) + ((am,) if want_argmax else ())
+    return res[0] if len(res) == 1 else res
 
 
 def swiglu(gate_up: torch.Tensor) -> torch.Tensor:

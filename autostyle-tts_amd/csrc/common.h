@@ -56,6 +56,11 @@ int gemm_scan(const _Float16* queries, const _Float16* bank, float* out, int32_t
               const float* col_scale = nullptr, const float* col_bias = nullptr, const float* row_qs = nullptr, float* blockmax = nullptr,
               int32_t bm_ld = 0);
 
+// the LM head with the log-sum-exp epilogue (ops_gemm.hip; the merge and the C entry: ops_score.hip): per (row, 256-column tile) the
+// pair (max, sum exp(y - max)) -> part[(m * nblk + tile) * 2], the column of the max -> idx[m * nblk + tile], logit[targets[m]] -> tgt[m]
+int gemm_head_lse(const _Float16* h, int32_t ldh, const _Float16* w, const float* bias, const int32_t* targets, int64_t rows, int32_t vocab,
+                  int32_t k, float* tgt, float* part, int32_t* idx, int32_t nblk, hipStream_t st);
+
 // an integer experiment switch from the environment (`dflt` when unset).  A set variable is reported once on stderr: these switches
 // change which kernel form runs (same results), and a stray one in a user's environment should not go unnoticed (runtime.hip)
 int exp_env_int(const char* name, int dflt);

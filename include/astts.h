@@ -606,6 +606,22 @@ typedef struct {            /* packed fp16 weight image (astts_op_pack_weight) +
     const void* w; const float* bias;
     int32_t n, cin, cin_pad, taps;
 } astts_weight_t;
+/* (embedder LLM, beside astts_op_argmax_rows / astts_op_sample_topk_topp above; here because it takes an astts_weight_t)
+ * Log-probability of given tokens under the LM head, with no logits plane (csrc/ops_score.hip; mirrored by tests/llm_scoring_ref.py):
+ *   logit[m][c] = <h[m], head row c> (+ head->bias[c]),  fp16 operands, fp32 accumulation, c in [0, vocab)
+ *   logprob[m]  = logit[m][targets[m]] - logsumexp(logit[m][0 .. vocab))
+ * h fp16 [rows, ldh >= hidden] (final-norm hidden states; 16-byte aligned, ldh a multiple of 8), head: the packed head weight
+ * (taps 1, hidden a multiple of 64), 1 <= vocab <= head->n (columns at or beyond vocab take no part), targets int32 [rows]:
+ * -1 -- or any value outside [0, vocab) -- means ignore: logprob[m] = 0 and ignored[m] = 1.  Optional outputs (NULL: not written):
+ * lse fp32 [rows] = the log-sum-exp, argmax int32 [rows] = the column of the largest logit (ties: the lowest index, as
+ * astts_op_argmax_rows), ignored int32 [rows].  The head GEMM's epilogue reduces every 256-column tile of a row to (max, sum of
+ * exp(y - max), column of the max) in the workspace (astts_op_head_logprob_workspace_bytes, 16-byte aligned) and a second kernel
+ * merges a row's tiles in a fixed order: no floating-point atomics, the same bits on every run, and a row's result does not depend
+ * on the other rows of the call.  rows >= 64 run the 256 x 256 eight-phase tile, fewer rows a 64 x 256 tile. */
+size_t astts_op_head_logprob_workspace_bytes(int64_t rows, int32_t vocab);
+int astts_op_head_logprob(const void* h_f16, int64_t ldh, const astts_weight_t* head, const int32_t* targets, int64_t rows, int32_t vocab,
+                          float* logprob, float* lse, int32_t* argmax, int32_t* ignored, void* workspace, size_t workspace_bytes,
+                          astts_stream_t stream);
 typedef struct {            /* ResnetBlock1D: conv3 -> GN -> Mish (+ time proj) -> conv3 -> GN -> Mish, + 1x1 res conv */
     astts_weight_t c1, mlp, c2, res;
     const float *g1_w, *g1_b, *g2_w, *g2_b;
