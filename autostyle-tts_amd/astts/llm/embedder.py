@@ -1,5 +1,5 @@
-"""The query embedder on the GPU: Llama-3.2 decoder forward -> mean-pooled last hidden state, and the greedy
-continuation that names the emotion.
+"""The query embedder on the GPU: Llama-3.2 decoder forward -> mean-pooled last hidden state, the greedy continuation that names
+the emotion, the sampled one that writes a biography, and the scoring of given continuations.
 
 Replaces, in the reference's retrieval scripts (paths under /root/reference):
     get_embedding(text, model, tokenizer, device, layer=-1, pooling='mean')   src/search_milvus.py:75-108
@@ -7,23 +7,10 @@ Replaces, in the reference's retrieval scripts (paths under /root/reference):
     generate_emotion_label(text, ...)  -> model.generate(do_sample=False)     milvus/search_json.py:154-198
     create_combined_embedding(...)     -> concatenate(emotion, biography)     milvus/search_json.py:201-229,
                                                                               src/search_milvus.py:214-221
-Every tensor operation is a HIP kernel of libastts.so (GEMMs: the MFMA family of csrc/ops_gemm.hip with fp16 activations;
-RMSNorm / RoPE / causal GQA attention at head_dim 128 / SwiGLU / mean-pool: csrc/ops_llm.hip).  fp16 weights and MFMA
-operands, fp32 residual stream, norms and softmax.  Parity: tests/test_llm_gpu.py against fixtures produced by transformers (fp32).
-
-``int8=True`` runs the reference's own numerics instead (src/search_milvus.py:47-62: a PEFT LoRA adapter over LLM.int8 weights):
-the seven projections of every layer become int8 weights with per-row scales, their inputs are quantised per row with the outlier
-columns of each sequence (|x| >= ``int8_threshold``) kept in fp16 against the dequantised weight, and the adapter's LoRA branch
-(``lora``: an astts.llm.peft.LoraAdapter) runs unmerged in fp32 -- all of it csrc/ops_int8.hip (DESIGN.md "LLM.int8 + LoRA").
-No fp16 copy of those projections is kept.  A ``lora`` without ``int8`` is merged into the fp16 weights at load.
-
-The tokenizer is the checkpoint's own (tokenizer.json: not available offline); anything with ``encode(text) -> list[int]``
-plugs in (`transformers.AutoTokenizer` when the checkpoint directory is given).  ``HashTokenizer`` is a labelled
-deterministic stand-in so that the CLIs run end to end without one.
+The model itself -- weights (fp16, or LLM.int8 + LoRA), RoPE tables, the layer stack -- is astts.llm.decoder.LlamaDecoder; the
+tokenizer protocol and its stand-in are astts.llm.tokenizer.
 """
 from __future__ import annotations
-
-import threading
 
 import math
 from typing import List, Optional, Sequence
@@ -32,152 +19,19 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..ops import PackedWeight
 from .config import LlamaShape
+from .decoder import LlamaDecoder, llama3_inv_freq  # noqa: F401  (llama3_inv_freq: imported from here by its users)
+from .tokenizer import HashTokenizer, decode_clean, encode_continuation
 
 
-def llama3_inv_freq(cfg: LlamaShape) -> torch.Tensor:
-    """transformers' _compute_llama3_parameters, float32 as there."""
-    inv = 1.0 / (cfg.rope_theta ** (torch.arange(0, cfg.head_dim, 2, dtype=torch.int64).float() / cfg.head_dim))
-    low_wl = cfg.rope_original_max_pos / cfg.rope_low_freq_factor
-    high_wl = cfg.rope_original_max_pos / cfg.rope_high_freq_factor
-    wl = 2 * math.pi / inv
-    inv_l = torch.where(wl > low_wl, inv / cfg.rope_factor, inv)
-    smooth = (cfg.rope_original_max_pos / wl - cfg.rope_low_freq_factor) / (cfg.rope_high_freq_factor - cfg.rope_low_freq_factor)
-    smoothed = (1 - smooth) * inv_l / cfg.rope_factor + smooth * inv_l
-    medium = ~(wl < high_wl) * ~(wl > low_wl)
-    return torch.where(medium, smoothed, inv_l)
-
-
-class HashTokenizer:
-    """STAND-IN (the Llama tokenizer files do not exist offline): bos + one id per whitespace-separated word by a fixed
-    hash.  Deterministic, reversible in nothing; good for plumbing and benchmarks only."""
-
-    def __init__(self, cfg: LlamaShape):
-        self.cfg = cfg
-
-    def encode(self, text: str, add_special_tokens: bool = True) -> List[int]:
-        import zlib
-
-        return ([self.cfg.bos_token_id] if add_special_tokens else []) + [3 + zlib.crc32(w.encode("utf-8")) % (self.cfg.vocab - 3)
-                                                                          for w in text.split()]
-
-    def decode(self, ids: Sequence[int]) -> str:
-        return " ".join(f"<{int(i)}>" for i in ids)
-
-
-class LlamaEmbedder:
-    def __init__(self, state: dict, cfg: LlamaShape, device=None, tokenizer=None, max_length: int = 512, int8: bool = False, lora=None,
-                 int8_threshold: float = 6.0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("astts.llm needs a ROCm GPU; there is no CPU fallback in the product path")
-        if cfg.head_dim != 128:
-            raise ValueError("LlamaEmbedder: the attention kernel is built for head_dim 128 (Llama-3.2)")
-        self.cfg = cfg
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+class LlamaEmbedder(LlamaDecoder):
+    def __init__(self, state: dict, cfg: LlamaShape, device=None, tokenizer=None, max_length: int = 512, int8: bool = False, lora=None, int8_threshold: float = 6.0):
+        super().__init__(state, cfg, device, int8=int8, lora=lora, int8_threshold=int8_threshold, rope_len=max(max_length, 16) + 64)
         self.tokenizer = tokenizer or HashTokenizer(cfg)
         self.max_length = max_length                                  # truncation=True, max_length=512: src/search_milvus.py:92
-        import os
-        self.mfma_attention = os.environ.get("ASTTS_LLM_ATTN", "mfma") != "valu"
-        self.int8, self.int8_threshold = bool(int8), float(int8_threshold)
-        if lora is not None and not self.int8:
-            state = _merge_lora(state, lora)
-        dev = self.device
-        with torch.cuda.device(dev):
-            f = lambda k: state[k].to(device=dev, dtype=torch.float32).contiguous()
-            self.embed = f("model.embed_tokens.weight")               # fp32 table: the lookup feeds the fp32 residual stream
-            self.L = []
-            for i in range(cfg.layers):
-                p = f"model.layers.{i}."
-                if self.int8:
-                    self.L.append(self._int8_layer(state, i, lora, dev))
-                    continue
-                wqkv = torch.cat([state[p + "self_attn.q_proj.weight"], state[p + "self_attn.k_proj.weight"],
-                                  state[p + "self_attn.v_proj.weight"]], 0)
-                wgu = torch.cat([state[p + "mlp.gate_proj.weight"], state[p + "mlp.up_proj.weight"]], 0)
-                self.L.append({"n1": f(p + "input_layernorm.weight"), "n2": f(p + "post_attention_layernorm.weight"),
-                               "wqkv": PackedWeight(wqkv, None, dev), "wo": PackedWeight(state[p + "self_attn.o_proj.weight"], None, dev),
-                               "wgu": PackedWeight(wgu, None, dev), "wd": PackedWeight(state[p + "mlp.down_proj.weight"], None, dev)})
-            self.norm = f("model.norm.weight")
-            head = state["model.embed_tokens.weight"] if cfg.tie_embeddings else state["lm_head.weight"]
-            self.head = PackedWeight(head, None, dev)
-            self._rope_lock = threading.Lock()
-            self._rope_tables(max(max_length, 16) + 64)
-
-    def _int8_layer(self, state: dict, i: int, lora, dev) -> dict:
-        p = f"model.layers.{i}."
-        pairs = {} if lora is None else lora.pairs
-        scaling = 1.0 if lora is None else lora.scaling
-
-        def w(*names):
-            parts = []
-            for nm in names:
-                ab = pairs.get((i, nm.split(".")[-1]))
-                parts.append((state[p + nm + ".weight"], None if ab is None else ab[0], None if ab is None else ab[1]))
-            if any(q[1] is not None for q in parts):          # a fused projection with LoRA on some parts: zero pairs on the others
-                r = next(q[1].shape[0] for q in parts if q[1] is not None)
-                parts = [q if q[1] is not None else (q[0], torch.zeros(r, q[0].shape[1]), torch.zeros(q[0].shape[0], r)) for q in parts]
-            return ops.Int8Weight(parts, scaling, dev)
-
-        f = lambda k: state[k].to(device=dev, dtype=torch.float32).contiguous()
-        return {"n1": f(p + "input_layernorm.weight"), "n2": f(p + "post_attention_layernorm.weight"),
-                "wqkv": w("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "wo": w("self_attn.o_proj"),
-                "wgu": w("mlp.gate_proj", "mlp.up_proj"), "wd": w("mlp.down_proj")}
-
-    def _lin(self, x: torch.Tensor, w, seg, residual=None, out_dtype=torch.float32) -> torch.Tensor:
-        """One projection: the fp16 GEMM (ops.linear), or with int8 the LLM.int8 + LoRA GEMM on the segments ``seg`` = (ids, count)."""
-        if self.int8:
-            return w(x, seg[0], seg[1], self.int8_threshold, residual=residual, out_dtype=out_dtype)
-        return ops.linear(x, w, residual=residual, out_dtype=out_dtype)
 
     def _is_eos(self, tok: int) -> bool:
         return tok == self.cfg.eos_token_id or tok in self.cfg.eos_token_ids
-
-    def _rope_tables(self, n: int) -> None:
-        """(cos, sin) rows for positions < n, published as ONE tuple: a thread that sees the new cos also sees the new sin."""
-        fr = torch.arange(n, dtype=torch.float32)[:, None] * llama3_inv_freq(self.cfg)[None, :]
-        self._rope = (fr.cos().to(self.device).contiguous(), fr.sin().to(self.device).contiguous())
-
-    @property
-    def cos(self) -> torch.Tensor:
-        return self._rope[0]
-
-    @property
-    def sin(self) -> torch.Tensor:
-        return self._rope[1]
-
-    # ------------------------------------------------------------------ the decoder stack
-    def hidden(self, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """ids int [B, T] (right-padded), lens int32 [B] or None -> final-norm hidden states fp32 [B, T, hidden]
-        (== outputs.hidden_states[-1] of LlamaModel)."""
-        cfg = self.cfg
-        b, t = ids.shape
-        if t > self._rope[0].shape[0]:  # the untruncated generation prompt (milvus/search_json.py:178) can exceed max_length
-            with self._rope_lock:
-                if t > self._rope[0].shape[0]:
-                    self._rope_tables((t + 255) // 256 * 256)
-        cos, sin = self._rope           # one consistent pair for the whole pass
-        hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
-        x = ops.embedding(self.embed, ids.to(self.device))
-        seg = None
-        if self.int8:                  # LLM.int8 segments: one per text; the right padding belongs to none
-            sid = torch.arange(b, dtype=torch.int32, device=self.device)[:, None].expand(b, t)
-            if lens is not None:
-                sid = torch.where(torch.arange(t, device=self.device)[None, :] < lens.to(self.device)[:, None], sid, -1)
-            seg = (sid.reshape(-1).to(torch.int32).contiguous(), b)
-        for L in self.L:
-            h = ops.rmsnorm(x, L["n1"], cfg.rms_eps)                              # fp16: its only consumer is an MFMA operand
-            qkv = self._lin(h, L["wqkv"], seg, out_dtype=torch.float16)          # [B, T, hq + 2 hk]
-            ops.rope_llama_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)             # q heads then k heads: contiguous
-            if self.mfma_attention:                                                # v_mfma_f32_32x32x16_f16 (csrc/ops_llm.hip attn_gqa_mfma)
-                a = ops.attn_gqa(qkv[..., :hq], qkv[..., hq:hq + hk], qkv[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens=lens)
-            else:                                                                  # the VALU kernel: the second implementation (tests)
-                a = ops.attn_causal_gqa(qkv[..., :hq], qkv[..., hq:hq + hk], qkv[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens)
-            x = self._lin(a, L["wo"], seg, residual=x)
-            h = ops.rmsnorm(x, L["n2"], cfg.rms_eps)
-            gu = self._lin(h, L["wgu"], seg, out_dtype=torch.float16)
-            x = self._lin(ops.swiglu(gu), L["wd"], seg, residual=x)
-        return ops.rmsnorm(x, self.norm, cfg.rms_eps, out_dtype=torch.float32)
 
     def embed_ids(self, ids: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Mean over each text's tokens of the last hidden state -> fp32 [B, hidden] on the GPU."""
@@ -206,9 +60,7 @@ class LlamaEmbedder:
         with a KV cache and no host synchronisation inside the loop: ONE pass over the prompts, then ``max_new_tokens - 1`` one-token
         steps; the argmax runs on the device (``astts_op_argmax_rows``) and feeds the next step's embedding lookup; the tokens come
         back in one copy at the end and are cut at each row's first EOS on the host (transformers stops a row there).
-        Layout: prompts are LEFT-padded to a common length, time-major ``[T, B]`` (the rows of a step are contiguous in the cache
-        ``[T_max, B, 2 * kv_heads * 128]`` per layer); ``key_start[b]`` masks a row's pad keys and shifts its RoPE positions so that its
-        first token has position 0, as in the one-at-a-time reference run."""
+        Prompts are LEFT-padded to a common length, time-major ``[T, B]``: the layout of ``hidden_cached``."""
         return self._generate_batch(prompts, max_new_tokens, lambda s, lg, out: ops.argmax_rows(lg, out=out))
 
     def _generate_batch(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, pick, keep_logits: bool = False, poll: int = 0):
@@ -222,48 +74,18 @@ class LlamaEmbedder:
         t, n_new = max(lens), int(max_new_tokens)
         if n_new <= 0:
             return ([list(p) for p in prompts], torch.empty((0, b, cfg.vocab), device=dev)) if keep_logits else [list(p) for p in prompts]
-        t_max = t + n_new
-        if t_max > self._rope[0].shape[0]:
-            with self._rope_lock:
-                if t_max > self._rope[0].shape[0]:
-                    self._rope_tables((t_max + 255) // 256 * 256)
-        cos, sin = self._rope
-        hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
         ids = torch.zeros((t, b), dtype=torch.int32)
         for j, p in enumerate(prompts):
             ids[t - lens[j]:, j] = torch.tensor(p, dtype=torch.int32)
         start = torch.tensor([t - n for n in lens], dtype=torch.int32, device=dev)
-        cache = [torch.empty((t_max, b, 2 * hk), dtype=torch.float16, device=dev) for _ in self.L]
+        cache = [torch.empty((t + n_new, b, 2 * cfg.kv_heads * cfg.head_dim), dtype=torch.float16, device=dev) for _ in self.L]
         toks = torch.zeros((n_new, b), dtype=torch.int32, device=dev)
-        seg_prefill = seg_step = None
-        if self.int8:                  # LLM.int8 segments: a prompt's tokens in the prefill (left padding: none), one row per decode step
-            bi = torch.arange(b, dtype=torch.int32, device=dev)
-            seg_prefill = (torch.where(torch.arange(t, dtype=torch.int32, device=dev)[:, None] >= start[None, :], bi[None, :], -1)
-                           .reshape(-1).to(torch.int32).contiguous(), b)
-            seg_step = (bi, b)
-
-        def stack(x: torch.Tensor, pos0: int) -> torch.Tensor:
-            """x fp32 [T', B, hidden] = the new positions pos0 .. pos0 + T' - 1 -> final-norm hidden of the LAST of them [B, hidden]."""
-            tn = x.shape[0]
-            seg = seg_prefill if pos0 == 0 else seg_step
-            for L, kv in zip(self.L, cache):
-                h = ops.rmsnorm(x, L["n1"], cfg.rms_eps)
-                qkv = self._lin(h, L["wqkv"], seg, out_dtype=torch.float16)                   # [T', B, hq + 2 hk]
-                ops.rope_llama_ex_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim, pos0=pos0, shift=start, time_major=True)
-                kv[pos0:pos0 + tn].copy_(qkv[..., hq:])                                        # K (rotated) | V into the cache rows
-                a = ops.attn_gqa(qkv[..., :hq], kv[:pos0 + tn, :, :hk], kv[:pos0 + tn, :, hk:], cfg.heads, cfg.kv_heads, cfg.head_dim,
-                                 key_start=start, pos0=pos0, time_major=True)
-                x = self._lin(a, L["wo"], seg, residual=x)
-                h = ops.rmsnorm(x, L["n2"], cfg.rms_eps)
-                gu = self._lin(h, L["wgu"], seg, out_dtype=torch.float16)
-                x = self._lin(ops.swiglu(gu), L["wd"], seg, residual=x)
-            return ops.rmsnorm(x[-1].contiguous(), self.norm, cfg.rms_eps, out_dtype=torch.float32)
-
+        seg_prefill, seg_step = self._segments(b, t, start=start), self._segments(b)          # LLM.int8: the prompts' tokens; one row per decode step
         logits = torch.empty((n_new, b, cfg.vocab), dtype=torch.float32, device=dev) if keep_logits else None
         eos = torch.tensor(sorted({int(cfg.eos_token_id), *(int(e) for e in cfg.eos_token_ids)}), dtype=torch.int32, device=dev) if poll > 0 else None
         x = ops.embedding(self.embed, ids.to(dev))
         for s in range(n_new):
-            h_last = stack(x, 0 if s == 0 else t + s - 1)
+            h_last = self.hidden_cached(x, cache, 0 if s == 0 else t + s - 1, start, seg_prefill if s == 0 else seg_step)
             lg = ops.linear(h_last, self.head)
             pick(s, lg, toks[s])
             if keep_logits:
@@ -348,24 +170,10 @@ class LlamaEmbedder:
         return ids, torch.tensor([len(s) for s in seqs], dtype=torch.int32)
 
     def _ids_of(self, x, continuation: bool = False) -> List[int]:
-        """Token ids of a text (or the ids themselves).  Tokenizer protocol: ``encode(text) -> ids`` (with whatever special tokens
-        the model expects in front) for prompts; a CONTINUATION carries no special tokens of its own, so a continuation given as
-        text needs ``encode(text, add_special_tokens=False)`` (transformers' signature; HashTokenizer has it).  A tokenizer without
-        that keyword cannot say what it adds: pass the continuation as token ids then."""
+        """Token ids of a text (or the ids themselves); a continuation carries no special tokens of its own (``encode_continuation``)."""
         if not isinstance(x, str):
             return [int(i) for i in x]
-        if not continuation:
-            return [int(i) for i in self.tokenizer.encode(x)]
-        import inspect
-        try:
-            ps = inspect.signature(self.tokenizer.encode).parameters
-            plain = "add_special_tokens" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
-        except (TypeError, ValueError):
-            plain = True
-        if not plain:
-            raise TypeError("score / classify: this tokenizer's encode() has no add_special_tokens keyword, so a continuation given as "
-                            "text cannot be tokenised without its special tokens; pass token ids")
-        return [int(i) for i in self.tokenizer.encode(x, add_special_tokens=False)]
+        return encode_continuation(self.tokenizer, x) if continuation else [int(i) for i in self.tokenizer.encode(x)]
 
     def score(self, prompts: Sequence, continuations: Sequence, batch: int = 32):
         """Per (prompt, continuation) pair: ``(logprobs, total)`` -- the log-probability of every continuation token given the prompt
@@ -417,8 +225,7 @@ class LlamaEmbedder:
 
     # ------------------------------------------------------------------ the reference's call surface
     def _encode(self, text: str) -> List[int]:
-        ids = list(self.tokenizer.encode(text))
-        return ids[: self.max_length]
+        return list(self.tokenizer.encode(text))[: self.max_length]
 
     def get_embedding(self, text: str) -> np.ndarray:
         """src/search_milvus.py:75-108 with layer=-1, pooling='mean' -> numpy float32 [hidden]."""
@@ -427,12 +234,8 @@ class LlamaEmbedder:
 
     def get_embeddings(self, texts: Sequence[str]) -> np.ndarray:
         """Many texts in one right-padded batch; each row equals get_embedding(text) (padding is masked)."""
-        enc = [self._encode(t) for t in texts]
-        tmax = max(len(e) for e in enc)
-        ids = torch.zeros((len(enc), tmax), dtype=torch.int64)
-        for i, e in enumerate(enc):
-            ids[i, : len(e)] = torch.tensor(e)
-        return self.embed_ids(ids, torch.tensor([len(e) for e in enc])).cpu().numpy()
+        ids, lens = self._pad_batch([self._encode(t) for t in texts])
+        return self.embed_ids(ids, lens).cpu().numpy()
 
     EMOTION_PROMPT = """\n=======
 Context: Given predefined emotional label set [happy, sad, neutral, angry, excited, frustrated], and below conversation:
@@ -452,8 +255,7 @@ Answer:"""
         """The labels of several utterances in one batched greedy decode (each equals generate_emotion_label of its text)."""
         prompts = [list(self.tokenizer.encode(self.EMOTION_PROMPT.format(t, t))) for t in texts]    # untruncated: only get_embedding truncates there
         outs = self.generate_greedy_batch(prompts, max_new_tokens)
-        dec = (lambda o: self.tokenizer.decode(o, skip_special_tokens=True)) if self._decode_takes_skip else self.tokenizer.decode   # search_json.py:191
-        return [dec(o).strip().lower() for o in outs]
+        return [decode_clean(self.tokenizer, o).strip().lower() for o in outs]                     # search_json.py:191
 
     BIOGRAPHY_PROMPT = """
 Given this conversation between speakers:
@@ -474,41 +276,16 @@ In overall of above conversation, what do you think about the characteristics of
         items = [(str(c), str(s)) for c, s in items]
         texts = [self.BIOGRAPHY_PROMPT.format(c, s) for c, s in items]
         prompts = [list(self.tokenizer.encode(t)) for t in texts]                                  # untruncated, as tokenizer(prompting) there
-        dec = (lambda o: self.tokenizer.decode(o, skip_special_tokens=True)) if self._decode_takes_skip else self.tokenizer.decode
         out: List[str] = []
         n_new = int(max_new_tokens)
         for c0 in range(0, len(items), max(int(batch), 1)):
             idx = range(c0, min(c0 + max(int(batch), 1), len(items)))
             u = torch.stack([self.row_uniforms(seed, first_index + i, max(n_new, 0)) for i in idx], 1)
             rows = self.generate_sample_batch([prompts[i] for i in idx], n_new, uniforms=u)
-            out.extend(dec(r).replace(texts[i], "").strip() for i, r in zip(idx, rows))       # :148-150
+            out.extend(decode_clean(self.tokenizer, r).replace(texts[i], "").strip() for i, r in zip(idx, rows))       # :148-150
         return out
-
-    @property
-    def _decode_takes_skip(self) -> bool:
-        """Decided from the tokenizer's signature, once: a TypeError raised INSIDE a real tokenizer's decode must not be mistaken for
-        "this stand-in has no skip_special_tokens argument" (and silently decoded with the special tokens in)."""
-        if not hasattr(self, "_decode_skip"):
-            import inspect
-            try:
-                ps = inspect.signature(self.tokenizer.decode).parameters
-                self._decode_skip = "skip_special_tokens" in ps or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in ps.values())
-            except (TypeError, ValueError):
-                self._decode_skip = True
-        return self._decode_skip
 
     def combined_embedding(self, emotion_text: str, biography_text: str) -> np.ndarray:
         """milvus/search_json.py:201-229 / src/search_milvus.py:214-221: [emotion | biography] float32, un-normalised."""
         e = self.get_embeddings([emotion_text, biography_text])
         return np.concatenate((e[0], e[1])).astype(np.float32)
-
-
-def _merge_lora(state: dict, lora) -> dict:
-    """W + scaling * B A in fp32 for the fp16 path (the int8 path keeps the branch unmerged, as peft does)."""
-    from .peft import PROJ
-
-    out = dict(state)
-    for (i, p), (a, b) in lora.pairs.items():
-        k = f"model.layers.{i}.{PROJ[p]}.weight"
-        out[k] = state[k].float() + lora.scaling * (b.float() @ a.float())
-    return out
