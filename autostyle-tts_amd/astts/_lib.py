@@ -6,8 +6,10 @@ this module raises.  Nothing here computes anything on the CPU.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
 
 # HIP multiplexes its streams onto GPU_MAX_HW_QUEUES hardware queues; streams that share a queue never overlap, and the chip's command
 # processor has FOUR pipes: queues that share a pipe take turns at every kernel boundary (two launch chains on such a pair run 2.4x slower
@@ -37,6 +39,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "4")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libastts.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "astts.h"))
 
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_RANGE = -1, -2, -3, -4, -5
@@ -56,53 +59,49 @@ class AsttsLibraryMissing(ImportError):
     pass
 
 
-_lib = None
+_CTYPES = {"void": None, "int": c_int32, "int32_t": c_int32, "int64_t": c_int64, "uint32_t": c_uint32, "size_t": c_size_t,
+           "float": c_float, "double": c_double, "astts_stream_t": c_void_p}
+_PROTOTYPE = re.compile(r"(?:^|(?<=[;{}]))\s*([\w\s*]+?)\b(astts_\w+)\s*\(([^()]*)\)\s*;")
 
-# name -> (restype, argtypes); mirrors include/astts.h one to one
-_SIGNATURES = {
-    "astts_abi_version": (c_int32, []),
-    "astts_last_error_string": (c_char_p, []),
-    "astts_knn_create": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, POINTER(c_void_p)]),
-    "astts_knn_destroy": (c_int32, [c_void_p]),
-    "astts_knn_info": (c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32)]),
-    "astts_knn_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
-    "astts_knn_search": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                   c_size_t, c_int32, c_void_p]),
-    "astts_knn_search_f64": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
-                                       c_size_t, c_int32, c_void_p]),
-    "astts_knn_search_masked": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                          c_size_t, c_int32, c_void_p]),
-    "astts_knn_last_fallbacks": (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int32)]),
-    "astts_knn_profile_enable": (c_int32, [c_void_p, c_int32]),
-    "astts_knn_profile_read": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_int64)]),
-    # frontend signal processing (astts/audio.py)
-    "astts_op_resample_poly": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_kaldi_fbank": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_float, c_float,
-                                       c_float, c_void_p]),
-    "astts_op_whisper_log_mel_workspace_bytes": (c_size_t, [c_int32]),
-    "astts_op_whisper_log_mel": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_void_p, c_size_t,
-                                           c_void_p]),
-    "astts_op_mel_spectrogram": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float,
-                                           c_void_p]),
-}
+
+def _ctype(decl: str, proto: str, returned: bool = False):
+    """One return type or parameter: a pointer is a c_void_p (a returned ``const char*`` a c_char_p), a scalar must be in _CTYPES."""
+    words = [w for w in decl.replace("*", " ").split() if w != "const"]
+    if "*" in decl:
+        return c_char_p if returned and words == ["char"] else c_void_p
+    if not words or words[0] not in _CTYPES:
+        raise ValueError(f"unknown type {' '.join(decl.split())!r} in `{proto}`: add it to astts/_lib.py:_CTYPES")
+    return _CTYPES[words[0]]
+
+
+def parse_prototypes(text: str) -> dict:
+    """name -> (restype, argtypes) of every ``type astts_name(args);`` of a C header."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)                              # comments
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)                                # preprocessor lines
+    text = re.sub(r"typedef\s+struct\s*\{[^{}]*\}", "typedef struct", text)         # struct bodies
+    sigs = {}
+    for m in _PROTOTYPE.finditer(text):
+        ret, name, args = m.groups()
+        proto = " ".join(f"{ret}{name}({args});".split())
+        params = [] if args.split() in ([], ["void"]) else args.split(",")
+        sigs[name] = (_ctype(ret, proto, returned=True), [_ctype(a, proto) for a in params])
+    return sigs
+
+
+@functools.lru_cache(maxsize=None)
+def signatures() -> dict:
+    """The C ABI as include/astts.h declares it: the header is the one place where a signature is written.  Parsed once."""
+    if not os.path.exists(HEADER_PATH):
+        raise AsttsLibraryMissing(f"{HEADER_PATH} not found: the ctypes signatures of libastts.so are derived from this header")
+    with open(HEADER_PATH) as f:
+        return parse_prototypes(f.read())
 
 
 def declared_symbols():
-    return sorted(_SIGNATURES)
+    return sorted(signatures())
 
 
-def register_signatures(sigs) -> None:
-    """Other host modules (ops) add their part of the ABI here before the first load()."""
-    _SIGNATURES.update(sigs)
-    if _lib is not None:
-        _bind(_lib, sigs)
-
-
-def _bind(lib, sigs) -> None:
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = res
-        fn.argtypes = args
+_lib = None
 
 
 def load():
@@ -115,7 +114,10 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"or `make -C autostyle-tts_amd/csrc`.  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    _bind(lib, _SIGNATURES)
+    for name, (res, args) in signatures().items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = res
+        fn.argtypes = args
     _lib = lib
     return lib
 

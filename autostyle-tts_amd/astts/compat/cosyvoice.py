@@ -42,7 +42,7 @@ def load_wav(path: str, target_sr: int) -> torch.Tensor:
 class _LmTokenStream:
     """The speech tokens of one segment WHILE the LM decodes them (``stream=True``).  Upstream runs ``llm.inference`` on a thread that
     appends to a list and lets ``tts()`` cut a chunk as soon as hop + look-ahead tokens are there; here the decode chain is issued in
-    ranges of steps (``AcousticLM.decode_range`` -> astts_lm_decode_range) by a worker thread on its OWN HIP stream, each range
+    ranges of steps (``AcousticLM.decode_range`` -> astts_lm_decode) by a worker thread on its OWN HIP stream, each range
     followed by an event and an asynchronous copy of its tokens to pinned memory, so that chunk k is rendered on the caller's stream
     while the chain decodes the tokens of chunk k + 1.  ``wait(n)`` returns the tokens so far once n exist (or all there will be):
     the interface ``synth.stream.stream_render`` takes in place of a finished token tensor."""

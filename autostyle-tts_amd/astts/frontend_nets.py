@@ -3,9 +3,9 @@ network that ``CosyVoice(model_dir)`` loads as ONNX files (/root/reference/tts_w
 on every prompt it is given (/root/reference/tts_with_rag.py:179-195, /root/reference/tts_with_style_and_timbre.py:83-93).
 
 Here both run as HIP kernels behind the C ABI -- no onnxruntime, no torch arithmetic:
-  SpeechTokenizerV1   128-bin Whisper log-mel (astts_op_whisper_log_mel) -> two convolutions (astts_op_gemm_ex, taps 3, GELU
+  SpeechTokenizerV1   128-bin Whisper log-mel (astts_op_whisper_log_mel) -> two convolutions (astts_op_gemm, taps 3, GELU
                       epilogue; the positions ride on the second one's residual operand) -> ``layers`` pre-norm blocks
-                      (astts_op_layernorm -> fused q | k | v projection -> astts_op_attn_mha_ex at head dimension 64 ->
+                      (astts_op_layernorm -> fused q | k | v projection -> astts_op_attn_mha at head dimension 64 ->
                       out-projection + residual -> LayerNorm -> FFN-in + exact GELU (fp16) -> FFN-out + residual) ->
                       astts_op_l2_normalize -> arg-min over the 4096-entry codebook = a k = 1 search of astts_knn_* under
                       ASTTS_METRIC_L2 (fp64-certified: the id is the exact arg-min of the frame this path computed)
@@ -20,24 +20,12 @@ torch is used for HBM buffers, views and layout transposes only.
 """
 from __future__ import annotations
 
-from ctypes import c_float, c_int32, c_int64, c_void_p
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib, audio, ops
 from .frontend_weights import CamPlusShape, SpeechTokenizerShape, sinusoids
-
-_lib.register_signatures({
-    "astts_op_affine_act": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p]),
-    "astts_op_freq_unfold": (c_int32, [c_void_p, c_int32, c_void_p] + [c_int32] * 7 + [c_void_p]),
-    "astts_op_ftc_to_tfc": (c_int32, [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p]),
-    "astts_op_cam_context": (c_int32, [c_void_p, c_int32, c_int64, c_void_p] + [c_int32] * 4 + [c_void_p]),
-    "astts_op_cam_gate": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64] + [c_int32] * 4 + [c_void_p]),
-    "astts_op_stats_pool": (c_int32, [c_void_p, c_int64, c_void_p] + [c_int32] * 3 + [c_void_p]),
-    "astts_op_l2_normalize": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
-    "astts_op_sub_time_mean": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p]),
-})
 
 SD = Dict[str, torch.Tensor]
 

@@ -60,7 +60,7 @@ class StyleBank:
         self._ws: Optional[torch.Tensor] = None
         self._ws_key: Tuple[int, int] = (0, 0)
         self._plans: dict = {}                       # (nq, k) -> (workspace tensor, aligned pointer, bytes)
-        self._search = lib.astts_knn_search_masked
+        self._search = lib.astts_knn_search
 
     def close(self) -> None:
         if getattr(self, "_h", None):

@@ -1,4 +1,4 @@
-"""Milvus boolean ``filter`` expressions -> a row mask (uint8 ``[N]``) for astts_knn_search_masked.
+"""Milvus boolean ``filter`` expressions -> a row mask (uint8 ``[N]``) for astts_knn_search.
 
 The reference passes ``filter=None`` everywhere (milvus/search_json.py:246-252, milvus/RAG.py:381-387), so this is the long
 tail of the ``MilvusClient.search`` surface: scalar filtering on the primary key and on the

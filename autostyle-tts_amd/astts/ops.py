@@ -8,67 +8,16 @@ from __future__ import annotations
 
 import ctypes
 import math
-from ctypes import c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_float, c_int32, c_int64, c_void_p
 from typing import Optional
 
 import torch
 
 from . import _lib
 
-_SIGS = {
-    "astts_op_pack_weight": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_gemm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32,
-                                c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                c_int32, c_int32, c_float, c_float, c_void_p]),
-    "astts_op_gemm_ex": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32,
-                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                   c_int32, c_int32, c_float, c_float, c_void_p]),
-    "astts_op_gemm_fused": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p] + [c_int32] * 11 + [c_float, c_float, c_void_p]),
-        "astts_op_gemm_fused_ws": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p] + [c_int32] * 11 + [c_float, c_float, c_void_p, c_size_t, c_void_p]),
-    "astts_op_gemm_fused_workspace_bytes": (c_size_t, []),
-    "astts_op_gemm_set_ring_mode": (c_int32, [c_int32]),
-    "astts_op_gemm_kernel_kind": (c_int32, [c_int64] + [c_int32] * 8),
-    "astts_op_gemm_ln": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64,
-                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_attn_relpos_ex": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
-                                          c_void_p, c_void_p] + [c_int32] * 8 + [c_int64] * 3 + [c_int32] * 3 + [c_float, c_void_p]),
-    "astts_prof_enable": (c_int32, [c_int32, c_int32, c_int32]),
-    "astts_prof_read": (c_int32, [c_int32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64),
-                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64)]),
-    "astts_op_layernorm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p]),
-    "astts_op_groupnorm_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
-    "astts_op_groupnorm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
-                                     c_int32, c_int32, c_float, c_int32, c_void_p, c_size_t, c_void_p]),
-    "astts_op_elementwise": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
-                                       c_int32, c_float, c_float, c_void_p]),
-    "astts_op_embedding": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p]),
-    "astts_op_interp_linear": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_interp_linear_ex": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
-    "astts_op_time_embedding": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p]),
-    "astts_op_attn_relpos": (c_int32, [c_void_p] * 8 + [c_int32] * 8 + [c_int64] * 3 + [c_int32] * 3 + [c_float, c_void_p]),
-    "astts_op_attn_mha_ex": (c_int32, [c_void_p] * 3 + [c_int32, c_void_p, c_void_p] + [c_int32] * 7 + [c_float, c_void_p]),
-    "astts_op_layernorm_ex": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p]),
-    "astts_op_layernorm_relu": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
-    "astts_op_groupnorm_ex": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
-                                        c_int32, c_int32, c_float, c_int32, c_void_p, c_size_t, c_void_p]),
-    "astts_op_attn_mha": (c_int32, [c_void_p] * 5 + [c_int32] * 6 + [c_float, c_void_p]),
-    "astts_op_nsf_source_workspace_bytes": (c_size_t, [c_int32, c_int32]),
-    "astts_op_nsf_source": (c_int32, [c_void_p] * 6 + [c_int32] * 4 + [c_float] * 4 + [c_void_p, c_size_t, c_void_p]),
-    "astts_op_stft16": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
-    "astts_op_istft16": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_float, c_float, c_void_p]),
-    "astts_op_stft16_lens": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
-    "astts_op_istft16_lens": (c_int32, [c_void_p, c_void_p, c_int32, c_int64, c_float, c_float, c_void_p, c_void_p]),
-    "astts_op_gemm_rows": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
-                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_gemm_lens": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32,
-                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                     c_int32, c_int32, c_float, c_float, c_void_p, c_void_p]),
-    "astts_op_ras_sample": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_float, c_int32, c_float, c_int32, c_int32, c_void_p]),
-}
 
-
+# mirrors of the header's structs, field for field (tests/test_abi_and_host.py compares them); the function signatures themselves are
+# read from include/astts.h by _lib
 class LmConfig(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("d", "heads", "ffn", "layers", "vocab_out", "speech_vocab", "pos_center", "pos_ld",
                                        "top_k", "ras_win")] + [(n, c_float) for n in ("top_p", "ras_tau", "eps")] + \
@@ -83,18 +32,6 @@ class LmGlobals(ctypes.Structure):
 class LmLayer(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in ("n1_g", "n1_b", "wqkv", "bqkv", "wo", "bo", "n2_g", "n2_b", "w1", "b1", "w2", "b2",
                                         "pos", "bias_u", "bias_v")]
-
-
-_SIGS.update({
-    "astts_op_ras_sample_ex": (c_int32, [c_void_p] * 4 + [c_int32] * 5 + [c_float, c_int32, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
-    "astts_lm_create": (c_int32, [ctypes.POINTER(LmConfig), ctypes.POINTER(LmGlobals), ctypes.POINTER(LmLayer), ctypes.POINTER(c_void_p)]),
-    "astts_lm_destroy": (c_int32, [c_void_p]),
-    "astts_lm_workspace_bytes": (c_size_t, [c_void_p, c_int32]),
-    "astts_lm_decode": (c_int32, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
-                                  c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "astts_lm_decode_range": (c_int32, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
-                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-})
 
 
 class Weight(ctypes.Structure):
@@ -126,58 +63,6 @@ class FlowConfig(ctypes.Structure):
 
 
 FLOW_RESAMPLE_NONE, FLOW_RESAMPLE_CONV, FLOW_RESAMPLE_DOWN, FLOW_RESAMPLE_UP = range(4)
-
-_SIGS.update({
-    "astts_stream_spin": (c_int32, [c_int32, c_void_p]),
-    "astts_stream_chain": (c_int32, [c_int32, c_int32, c_int32, c_void_p]),
-    "astts_stream_create_cu_mask": (c_int32, [ctypes.POINTER(ctypes.c_uint32), c_int32, ctypes.POINTER(c_void_p)]),
-    "astts_stream_destroy": (c_int32, [c_void_p]),
-    "astts_selftest_xlane": (c_int32, [ctypes.POINTER(c_int32), c_void_p]),
-    "astts_flow_create": (c_int32, [ctypes.POINTER(FlowConfig), ctypes.POINTER(FlowBlock), ctypes.POINTER(FlowBlock),
-                                    ctypes.POINTER(FlowBlock), ctypes.POINTER(c_void_p)]),
-    "astts_flow_destroy": (c_int32, [c_void_p]),
-    "astts_flow_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
-    "astts_flow_solve": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
-                                   ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_float, c_void_p, c_size_t, c_void_p]),
-})
-_SIGS.update({   # fused transformer-block front half of the flow estimator (csrc/ops_tfm_fused.hip)
-    "astts_op_tfm_attn_fused_supported": (c_int32, [c_int32, c_int32, c_int32]),
-    "astts_op_tfm_pack_frag": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
-    # the flow engine's forms (L2 prefetch of the next launch's weights): called from C++, declared here for the ABI table
-    "astts_op_tfm_attn_fused_pf": (c_int32, [c_void_p] * 5 + [c_int32] * 4 + [c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p]),
-    "astts_op_tfm_ffn_fused_pf": (c_int32, [c_void_p] * 6 + [c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_int32,
-                                            c_void_p, ctypes.c_uint32, c_void_p]),
-    "astts_op_conv_pack_frag": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_resnet_conv_stats_floats": (c_size_t, [c_int32, c_int32]),
-    "astts_op_resnet_conv_supported": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
-    "astts_op_resnet_conv": (c_int32, [c_void_p] * 14 + [c_int32] * 4 + [c_float, c_void_p]),
-    "astts_op_resnet_conv_pf": (c_int32, [c_void_p] * 14 + [c_int32] * 4 + [c_float, c_void_p, ctypes.c_uint32, c_void_p]),
-    "astts_op_conv1d_snake_supported": (c_int32, [c_int32, c_int32, c_int32]),
-    "astts_op_conv1d_snake": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_float,
-                                        c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_conv1d_snake_lens": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_float,
-                                             c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
-    "astts_op_tfm_ffn_fused_supported": (c_int32, [c_int32, c_int32]),
-    "astts_op_tfm_ffn_fused": (c_int32, [c_void_p] * 6 + [c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
-    "astts_op_tfm_attn_fused": (c_int32, [c_void_p] * 5 + [c_int32] * 4 + [c_float, c_float, c_void_p]),
-})
-_SIGS.update({   # query-embedder operators (csrc/ops_llm.hip)
-    "astts_op_rmsnorm": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p]),
-    "astts_op_rope_llama": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p]),
-    "astts_op_attn_causal_gqa": (c_int32, [c_void_p] * 5 + [c_int32] * 8 + [c_float, c_void_p]),
-    "astts_op_swiglu": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_mean_pool": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_attn_gqa": (c_int32, [c_void_p] * 6 + [c_int32] * 7 + [c_int64] * 6 + [c_float, c_void_p]),
-    "astts_op_rope_llama_ex": (c_int32, [c_void_p] * 4 + [c_int32] * 7 + [c_void_p]),
-    "astts_op_argmax_rows": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p]),
-    "astts_op_sample_topk_topp": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32, c_float, c_void_p]),
-})
-_SIGS.update({   # token log-probabilities under the LM head without a logits plane (csrc/ops_score.hip)
-    "astts_op_head_logprob_workspace_bytes": (c_size_t, [c_int64, c_int32]),
-    "astts_op_head_logprob": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_size_t, c_void_p]),
-})
-_lib.register_signatures(_SIGS)
 
 ACT = {"none": 0, "relu": 1, "silu": 2, "swish": 2, "gelu": 3, "mish": 4, "elu": 5, "tanh": 6, "leaky": 7}
 EL_SNAKE, EL_LEAKY, EL_ADD, EL_MUL_ROWMASK, EL_ADD_BC, EL_SCALE, EL_CFG_EULER, EL_MISH, EL_SILU, EL_CLAMP, EL_TANH, EL_ELU, EL_RELU_SCALE = range(13)
@@ -257,7 +142,7 @@ def gemm(x: torch.Tensor, w: PackedWeight, act: str = "none", residual: Optional
          in_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``x``: ``[..., cin]`` fp32 or fp16 (rows = batch*time); conv geometry via t_in/t_out/stride/dil/pad.
     ``out_dtype=torch.float16`` when the result only feeds MFMA consumers (another GEMM / attention).
-    ``in_lens`` (int32 ``[batches]``, ragged batches): input steps at or beyond a row's length read as zero (astts_op_gemm_lens)."""
+    ``in_lens`` (int32 ``[batches]``, ragged batches): input steps at or beyond a row's length read as zero."""
     x = _act_in(x)
     cin = x.shape[-1]
     assert cin == w.cin, (cin, w.cin)
@@ -278,15 +163,10 @@ def gemm(x: torch.Tensor, w: PackedWeight, act: str = "none", residual: Optional
         ldr = residual.shape[-1]
     if in_lens is not None:
         assert in_lens.dtype == torch.int32 and in_lens.numel() == batches and in_lens.is_cuda
-        _lib.check(_L().astts_op_gemm_lens(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, w.data.data_ptr(),
-                                           _p(w.bias) if use_bias else None, _p(residual), _p(row_scale), out.data_ptr(),
-                                           1 if out.dtype == torch.float16 else 0, m, w.n, w.cin, w.cin_pad, w.taps, cin, ldc, ldr,
-                                           t_in, t_out, stride, dil, pad, ACT[act], alpha, slope, in_lens.data_ptr(), _st()))
-        return out
-    _lib.check(_L().astts_op_gemm_ex(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, w.data.data_ptr(),
-                                     _p(w.bias) if use_bias else None, _p(residual), _p(row_scale), out.data_ptr(),
-                                     1 if out.dtype == torch.float16 else 0, m, w.n, w.cin, w.cin_pad, w.taps, cin, ldc, ldr,
-                                     t_in, t_out, stride, dil, pad, ACT[act], alpha, slope, _st()))
+    _lib.check(_L().astts_op_gemm(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, w.data.data_ptr(),
+                                  _p(w.bias) if use_bias else None, _p(residual), _p(row_scale), out.data_ptr(),
+                                  1 if out.dtype == torch.float16 else 0, m, w.n, w.cin, w.cin_pad, w.taps, cin, ldc, ldr,
+                                  t_in, t_out, stride, dil, pad, ACT[act], alpha, slope, _p(in_lens), _st()))
     return out
 
 
@@ -324,13 +204,13 @@ def gemm_fused(x: torch.Tensor, w: PackedWeight, m: int, gather: Optional[torch.
     if ws is None:      # zeroed once per (device, stream): the kernel leaves its arrival counters at zero
         ws = _SPLITK_WS[(x.device.index, st)] = torch.zeros(int(_L().astts_op_gemm_fused_workspace_bytes()), dtype=torch.uint8,
                                                             device=x.device)
-    _lib.check(_L().astts_op_gemm_fused_ws(x.data_ptr(), _p(gather), _p(ga), _p(be), ln_eps, w.data.data_ptr(), _p(w.bias),
-                                           _p(residual), out.data_ptr(), _p(out2),
-                                           1 if (out2 is not None and out2.dtype == torch.float16) else 0, m, w.n, n_split, w.cin,
-                                           w.cin_pad, lda if lda is not None else x.stride(-2), out.stride(-2),
-                                           out2.stride(-2) if out2 is not None else 0,
-                                           residual.stride(-2) if residual is not None else 0, ACT[act], alpha, slope,
-                                           ws.data_ptr(), ws.numel(), st))
+    _lib.check(_L().astts_op_gemm_fused(x.data_ptr(), _p(gather), _p(ga), _p(be), ln_eps, w.data.data_ptr(), _p(w.bias),
+                                        _p(residual), out.data_ptr(), _p(out2),
+                                        1 if (out2 is not None and out2.dtype == torch.float16) else 0, m, w.n, n_split, w.cin,
+                                        w.cin_pad, lda if lda is not None else x.stride(-2), out.stride(-2),
+                                        out2.stride(-2) if out2 is not None else 0,
+                                        residual.stride(-2) if residual is not None else 0, ACT[act], alpha, slope,
+                                        ws.data_ptr(), ws.numel(), st))
     return out
 
 
@@ -426,8 +306,8 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     x = _f32(x)
     c = x.shape[-1]
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    _lib.check(_L().astts_op_layernorm_relu(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
-                                            1 if out_dtype == torch.float16 else 0, x.numel() // c, c, c, c, eps, relu_scale, _st()))
+    _lib.check(_L().astts_op_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+                                       1 if out_dtype == torch.float16 else 0, x.numel() // c, c, c, c, eps, relu_scale, _st()))
     return y
 
 
@@ -439,9 +319,9 @@ def groupnorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: 
     need = int(_L().astts_op_groupnorm_workspace_bytes(b, t, groups))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    _lib.check(_L().astts_op_groupnorm_ex(x.data_ptr(), _p(lens), gamma.data_ptr(), beta.data_ptr(), _p(add_bc),
-                                          y.data_ptr(), 1 if out_dtype == torch.float16 else 0, b, t, c, groups, eps,
-                                          1 if mish else 0, ws.data_ptr(), need, _st()))
+    _lib.check(_L().astts_op_groupnorm(x.data_ptr(), _p(lens), gamma.data_ptr(), beta.data_ptr(), _p(add_bc),
+                                       y.data_ptr(), 1 if out_dtype == torch.float16 else 0, b, t, c, groups, eps,
+                                       1 if mish else 0, ws.data_ptr(), need, _st()))
     return y
 
 
@@ -472,7 +352,7 @@ def interp_linear(x: torch.Tensor, t_out: int, in_lens: Optional[torch.Tensor] =
     x = _f32(x)
     b, t, c = x.shape
     y = torch.empty((b, t_out, c), dtype=torch.float32, device=x.device)
-    _lib.check(_L().astts_op_interp_linear_ex(x.data_ptr(), y.data_ptr(), b, t, t_out, c, _p(in_lens), _p(out_lens), _st()))
+    _lib.check(_L().astts_op_interp_linear(x.data_ptr(), y.data_ptr(), b, t, t_out, c, _p(in_lens), _p(out_lens), _st()))
     return y
 
 
@@ -501,11 +381,11 @@ def attn_relpos(q, k, v, pos, bias_u, bias_v, heads: int, lens=None, q_pos0: int
             out = torch.empty((b, tq, heads * 64), dtype=torch.float32, device=q.device)
         ldo, o_bs = out.stride(1), out.stride(0)
     assert v.stride() == k.stride() and k.dtype == v.dtype
-    _lib.check(_L().astts_op_attn_relpos_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), 1 if k.dtype == torch.float16 else 0,
-                                            pos.data_ptr(), 1 if pos.dtype == torch.float16 else 0, bias_u.data_ptr(),
-                                            bias_v.data_ptr(), _p(lens), _p(key_start), out.data_ptr(), b, heads, tq, tk, ldq, ldk, ldo,
-                                            pos.stride(0), q_bs, k_bs, o_bs, q_pos0, pos_center, 1 if causal else 0,
-                                            1.0 / math.sqrt(64.0), _st()))
+    _lib.check(_L().astts_op_attn_relpos(q.data_ptr(), k.data_ptr(), v.data_ptr(), 1 if k.dtype == torch.float16 else 0,
+                                         pos.data_ptr(), 1 if pos.dtype == torch.float16 else 0, bias_u.data_ptr(),
+                                         bias_v.data_ptr(), _p(lens), _p(key_start), out.data_ptr(), b, heads, tq, tk, ldq, ldk, ldo,
+                                         pos.stride(0), q_bs, k_bs, o_bs, q_pos0, pos_center, 1 if causal else 0,
+                                         1.0 / math.sqrt(64.0), _st()))
     return out
 
 
@@ -514,9 +394,9 @@ def attn_mha(q, k, v, heads: int, lens=None, out_dtype=torch.float32) -> torch.T
     b, t = q.shape[0], q.shape[1]
     out = torch.empty((b, t, heads * 64), dtype=out_dtype, device=q.device)
     assert q.stride(0) == t * q.stride(1) and k.stride(0) == t * k.stride(1) and q.dtype == k.dtype == v.dtype
-    _lib.check(_L().astts_op_attn_mha_ex(q.data_ptr(), k.data_ptr(), v.data_ptr(), 1 if q.dtype == torch.float16 else 0,
-                                         _p(lens), out.data_ptr(), 1 if out_dtype == torch.float16 else 0, b, heads, t,
-                                         q.stride(1), k.stride(1), heads * 64, 1.0 / math.sqrt(64.0), _st()))
+    _lib.check(_L().astts_op_attn_mha(q.data_ptr(), k.data_ptr(), v.data_ptr(), 1 if q.dtype == torch.float16 else 0,
+                                      _p(lens), out.data_ptr(), 1 if out_dtype == torch.float16 else 0, b, heads, t,
+                                      q.stride(1), k.stride(1), heads * 64, 1.0 / math.sqrt(64.0), _st()))
     return out
 
 
@@ -549,7 +429,7 @@ def resnet_conv(x: torch.Tensor, w: PackedWeight, w_frag: torch.Tensor, lens=Non
     i_s, i_g, i_b = in_gn if in_gn is not None else (None, None, None)
     r_h, r_s, r_g, r_b = res_gn if res_gn is not None else (None, None, None, None)
     _lib.check(_L().astts_op_resnet_conv(x.data_ptr(), w_frag.data_ptr(), _p(w.bias), out.data_ptr(), _p(i_s), _p(i_g), _p(i_b), _p(in_add),
-                                         _p(r_h), _p(r_s), _p(r_g), _p(r_b), _p(stats), _p(lens), b, t, c, w.taps, eps, _st()))
+                                         _p(r_h), _p(r_s), _p(r_g), _p(r_b), _p(stats), _p(lens), b, t, c, w.taps, eps, None, 0, _st()))
     return (out, stats) if want_stats else out
 
 
@@ -571,9 +451,9 @@ def conv1d_snake(x: torch.Tensor, w: PackedWeight, w_frag: torch.Tensor, dil: in
         assert residual.shape == x.shape
     if acc is not None:
         assert acc.dtype == torch.float32 and acc.is_contiguous() and acc.shape == x.shape
-    _lib.check(_L().astts_op_conv1d_snake_lens(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, _p(alpha), w_frag.data_ptr(), _p(w.bias),
-                                               _p(residual), _p(y), 1 if out_dtype == torch.float16 else 0, _p(acc), acc_scale,
-                                               1 if acc_add else 0, b, l, c, w.taps, dil, _p(lens), _st()))
+    _lib.check(_L().astts_op_conv1d_snake(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, _p(alpha), w_frag.data_ptr(), _p(w.bias),
+                                          _p(residual), _p(y), 1 if out_dtype == torch.float16 else 0, _p(acc), acc_scale,
+                                          1 if acc_add else 0, b, l, c, w.taps, dil, _p(lens), _st()))
     return y
 
 
@@ -606,7 +486,8 @@ def tfm_ffn_fused(x: torch.Tensor, w1: PackedWeight, w1_frag: torch.Tensor, w2: 
         assert attn.dtype == torch.float16 and attn.is_contiguous() and attn.numel() // k0 == m
         assert wo is not None and wo.n == c and wo.cin == k0 and wo_frag.shape == (c, k0)
     _lib.check(_L().astts_op_tfm_ffn_fused(x.data_ptr(), w1_frag.data_ptr(), _p(w1.bias), w2_frag.data_ptr(), _p(w2.bias), out.data_ptr(),
-                                           m, c, hidden, eps, _p(attn), _p(wo_frag), _p(wo.bias) if wo is not None else None, k0, _st()))
+                                           m, c, hidden, eps, _p(attn), _p(wo_frag), _p(wo.bias) if wo is not None else None, k0, None, 0,
+                                           _st()))
     return out
 
 
@@ -619,7 +500,7 @@ def tfm_attn_fused(x: torch.Tensor, wqkv: PackedWeight, wqkv_frag: torch.Tensor,
     assert wqkv.cin == c == wqkv.cin_pad and wqkv.n == 3 * heads * 64 and wqkv_frag.shape == (wqkv.n, c)
     out = torch.empty((b, t, heads * 64), dtype=torch.float16, device=x.device)
     _lib.check(_L().astts_op_tfm_attn_fused(x.data_ptr(), wqkv_frag.data_ptr(), _p(wqkv.bias), _p(lens), out.data_ptr(), b, heads, t, c, eps,
-                                            1.0 / math.sqrt(64.0), _st()))
+                                            1.0 / math.sqrt(64.0), None, None, 0, _st()))
     return out
 
 
@@ -641,7 +522,7 @@ def stft16(x: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Tensor
     x = _f32(x)
     b, n = x.shape
     y = torch.empty((b, n // 4 + 1, 18), dtype=torch.float32, device=x.device)
-    _lib.check(_L().astts_op_stft16_lens(x.data_ptr(), y.data_ptr(), b, n, _p(lens), _st()))
+    _lib.check(_L().astts_op_stft16(x.data_ptr(), y.data_ptr(), b, n, _p(lens), _st()))
     return y
 
 
@@ -650,7 +531,7 @@ def istft16(y: torch.Tensor, mag_clip: float = 100.0, audio_limit: float = 0.99,
     y = _f32(y)
     b, f, _ = y.shape
     wav = torch.empty((b, 4 * (f - 1)), dtype=torch.float32, device=y.device)
-    _lib.check(_L().astts_op_istft16_lens(y.data_ptr(), wav.data_ptr(), b, f, mag_clip, audio_limit, _p(frame_lens), _st()))
+    _lib.check(_L().astts_op_istft16(y.data_ptr(), wav.data_ptr(), b, f, mag_clip, audio_limit, _p(frame_lens), _st()))
     return wav
 
 
@@ -971,18 +852,6 @@ def mean_pool(x: torch.Tensor, lens: Optional[torch.Tensor] = None) -> torch.Ten
 
 
 # ---------------------------------------------------------------------------------------------- LLM.int8 + LoRA (csrc/ops_int8.hip)
-_I8_SIGS = {
-    "astts_op_i8_quant_weight": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
-    "astts_op_i8_quant_act_workspace_bytes": (c_size_t, [c_int32, c_int32]),
-    "astts_op_i8_quant_act": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
-                                        c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "astts_op_i8_lora_down": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
-    "astts_op_i8_gemm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
-                                   c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_int64,
-                                   c_void_p, c_int32, c_int64, c_void_p]),
-}
-_SIGS.update(_I8_SIGS)
-_lib.register_signatures(_I8_SIGS)
 
 I8_OUT_F32, I8_OUT_F16, I8_OUT_ACC = range(3)
 

@@ -318,7 +318,7 @@ class AcousticLM:
 
     def decode_range(self, ctx, s_end: Optional[int] = None) -> None:
         """Enqueue decode steps [ctx["next"], s_end) on the CURRENT stream (one C++ call, no host synchronisation).  The ranges of
-        one decode must be issued in order on one stream (astts_lm_decode_range)."""
+        one decode must be issued in order on one stream (astts_lm_decode)."""
         import ctypes
 
         from .. import _lib
@@ -329,12 +329,12 @@ class AcousticLM:
         if s_end <= s_begin:
             return
         ptrs = (ctypes.c_void_p * len(cache))(*[c.data_ptr() for c in cache])
-        _lib.check(lib.astts_lm_decode_range(self._engine(), ctx["logits0"].data_ptr(), ptrs, None if key_start is None else key_start.data_ptr(),
-                                             s0 + n_steps, b, s0, n_steps, s_begin, s_end, ctx["u"].data_ptr(),
-                                             None if ctx["forced"] is None else ctx["forced"].data_ptr(), self._eos_min(ignore_eos, n_steps),
-                                             ignore_eos.data_ptr() if torch.is_tensor(ignore_eos) else None, ctx["toks"].data_ptr(),
-                                             None if ctx["logits"] is None else ctx["logits"].data_ptr(), ctx["ws_aligned"], ctx["ws_bytes"],
-                                             _lib.stream_ptr()))
+        _lib.check(lib.astts_lm_decode(self._engine(), ctx["logits0"].data_ptr(), ptrs, None if key_start is None else key_start.data_ptr(),
+                                       s0 + n_steps, b, s0, n_steps, s_begin, s_end, ctx["u"].data_ptr(),
+                                       None if ctx["forced"] is None else ctx["forced"].data_ptr(), self._eos_min(ignore_eos, n_steps),
+                                       ignore_eos.data_ptr() if torch.is_tensor(ignore_eos) else None, ctx["toks"].data_ptr(),
+                                       None if ctx["logits"] is None else ctx["logits"].data_ptr(), ctx["ws_aligned"], ctx["ws_bytes"],
+                                       _lib.stream_ptr()))
         ctx["next"] = s_end
 
     def decode_prefilled(self, state, uniforms: torch.Tensor, ignore_eos: bool = True, forced_tokens: Optional[torch.Tensor] = None,

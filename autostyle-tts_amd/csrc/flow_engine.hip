@@ -5,7 +5,7 @@
 // One solve = n_steps x (2 down + 12 mid + 2 up) U-Net blocks, each a ResnetBlock1D and 4 transformer
 // blocks: ~520 launches per step.  A Python host needs as long to enqueue them (~10 us each) as the GPU
 // needs to run them, which both caps the stage and starves the other pipeline threads of the GIL; this
-// engine issues the same operator sequence (astts_op_gemm_ex / groupnorm_ex / layernorm_ex /
+// engine issues the same operator sequence (astts_op_gemm / groupnorm / layernorm /
 // attn_mha_ex / elementwise: bit-identical results to the operator-by-operator path) from C++.
 //
 // Data layout: activations [2b, t, C] row-major (time-major rows, channels contiguous), rows [0, b) the
@@ -163,8 +163,8 @@ struct Ctx {
 
     int gemm(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
              int t_in, int t_out, int stride, int pad, int act) const {
-        return astts_op_gemm_ex(x, x16, w.w, w.bias, residual, nullptr, out, out16, m, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
-                                residual ? w.n : 0, t_in, t_out, stride, 1, pad, act, 1.0f, 0.1f, st);
+        return astts_op_gemm(x, x16, w.w, w.bias, residual, nullptr, out, out16, m, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
+                             residual ? w.n : 0, t_in, t_out, stride, 1, pad, act, 1.0f, 0.1f, nullptr, st);
     }
     int linear(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m, int act) const {
         return gemm(x, x16, w, residual, out, out16, m, (int)m, (int)m, 1, 0, act);
@@ -186,17 +186,17 @@ struct Ctx {
             // three launches, GroupNorm + Mish folded into the convolutions (ops_resnet_conv.hip)
             // every launch requests the NEXT one's (cold) weights into L2 while it runs
             auto wbytes = [](const astts_weight_t& w) { return (uint32_t)((size_t)w.n * w.taps * w.cin_pad * 2); };
-            RUN(astts_op_resnet_conv_pf(x, r.c1_frag, r.c1.bias, B.r1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                        B.rstat1, lens, b2, t, r.c1.cin, r.c1.taps, 1e-5f, r.c2_frag, wbytes(r.c2), st));
-            RUN(astts_op_resnet_conv_pf(B.r1, r.c2_frag, r.c2.bias, B.r2, B.rstat1, r.g1_w, r.g1_b, tproj, nullptr, nullptr, nullptr, nullptr,
-                                        B.rstat2, lens, b2, t, r.c2.cin, r.c2.taps, 1e-5f, r.res_frag, wbytes(r.res), st));
-            return astts_op_resnet_conv_pf(x, r.res_frag, r.res.bias, out, nullptr, nullptr, nullptr, nullptr, B.r2, B.rstat2, r.g2_w, r.g2_b,
-                                           nullptr, lens, b2, t, r.res.cin, r.res.taps, 1e-5f, next_w, next_bytes, st);
+            RUN(astts_op_resnet_conv(x, r.c1_frag, r.c1.bias, B.r1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                     B.rstat1, lens, b2, t, r.c1.cin, r.c1.taps, 1e-5f, r.c2_frag, wbytes(r.c2), st));
+            RUN(astts_op_resnet_conv(B.r1, r.c2_frag, r.c2.bias, B.r2, B.rstat1, r.g1_w, r.g1_b, tproj, nullptr, nullptr, nullptr, nullptr,
+                                     B.rstat2, lens, b2, t, r.c2.cin, r.c2.taps, 1e-5f, r.res_frag, wbytes(r.res), st));
+            return astts_op_resnet_conv(x, r.res_frag, r.res.bias, out, nullptr, nullptr, nullptr, nullptr, B.r2, B.rstat2, r.g2_w, r.g2_b,
+                                        nullptr, lens, b2, t, r.res.cin, r.res.taps, 1e-5f, next_w, next_bytes, st);
         }
         RUN(gemm(x, 0, r.c1, nullptr, B.r1, 0, rows, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(astts_op_groupnorm_ex(B.r1, lens, r.g1_w, r.g1_b, tproj, B.r1h, 1, b2, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
+        RUN(astts_op_groupnorm(B.r1, lens, r.g1_w, r.g1_b, tproj, B.r1h, 1, b2, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
         RUN(gemm(B.r1h, 1, r.c2, nullptr, B.r2, 0, rows, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(astts_op_groupnorm_ex(B.r2, lens, r.g2_w, r.g2_b, nullptr, B.r3, 0, b2, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
+        RUN(astts_op_groupnorm(B.r2, lens, r.g2_w, r.g2_b, nullptr, B.r3, 0, b2, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
         return gemm(x, 0, r.res, B.r3, out, 0, rows, t, t, 1, 0, ASTTS_ACT_NONE);     // res_conv(x) + h
     }
 
@@ -214,24 +214,25 @@ struct Ctx {
             // requested into L2 from here
             const void* pf[3] = {w.wo_frag, w.w1_frag, w.w2_frag};
             const uint32_t pfb[3] = {(uint32_t)((size_t)C * hd * 2), (uint32_t)((size_t)w.w1.n * C * 2), (uint32_t)((size_t)C * w.w1.n * 2)};
-            RUN(astts_op_tfm_attn_fused_pf(p, w.qkv_frag, w.qkv.bias, lens, B.a16, b2, heads, t, C, 1e-5f, 0.125f, pf, pfb,
-                                           (w.wo_frag && w.w1_frag && w.w2_frag) ? 3 : 0, st));
+            RUN(astts_op_tfm_attn_fused(p, w.qkv_frag, w.qkv.bias, lens, B.a16, b2, heads, t, C, 1e-5f, 0.125f, pf, pfb,
+                                        (w.wo_frag && w.w1_frag && w.w2_frag) ? 3 : 0, st));
         } else {
-            RUN(astts_op_layernorm_ex(p, w.n1_w, w.n1_b, B.n16, 1, rows, C, C, C, 1e-5f, st));
+            RUN(astts_op_layernorm(p, w.n1_w, w.n1_b, B.n16, 1, rows, C, C, C, 1e-5f, 0.0f, st));
             RUN(linear(B.n16, 1, w.qkv, nullptr, B.qkv16, 1, rows, ASTTS_ACT_NONE));
-            RUN(astts_op_attn_mha_ex(B.qkv16, B.qkv16 + hd, B.qkv16 + 2 * hd, 1, lens, B.a16, 1, b2, heads, t, 3 * hd, 3 * hd, hd,
-                                     0.125f, st));
+            RUN(astts_op_attn_mha(B.qkv16, B.qkv16 + hd, B.qkv16 + 2 * hd, 1, lens, B.a16, 1, b2, heads, t, 3 * hd, 3 * hd, hd,
+                                  0.125f, st));
         }
         const bool ffn = w.w1_frag && w.w2_frag && astts_op_tfm_ffn_fused_supported(C, w.w1.n);
         // output projection + residual + LayerNorm + W1 + GELU + W2 + residual in one launch (in place on p); faster than the
         // separate projection at every row count measured (5 504: 20.2 vs 26.8 us, 11 008: 36.6 vs 45.0, 44 032: 116 vs 128)
         if (ffn && w.wo_frag && (hd == 256 || hd == 512))
-            return astts_op_tfm_ffn_fused_pf(p, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, B.a16, w.wo_frag,
-                                             w.wo.bias, hd, next_w, next_bytes, st);
+            return astts_op_tfm_ffn_fused(p, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, B.a16, w.wo_frag,
+                                          w.wo.bias, hd, next_w, next_bytes, st);
         RUN(linear(B.a16, 1, w.wo, p, q, 0, rows, ASTTS_ACT_NONE));
         if (ffn)      // LayerNorm + W1 + GELU + W2 + residual: one launch
-            return astts_op_tfm_ffn_fused(q, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, nullptr, nullptr, nullptr, 0, st);
-        RUN(astts_op_layernorm_ex(q, w.n3_w, w.n3_b, B.n16, 1, rows, C, C, C, 1e-5f, st));
+            return astts_op_tfm_ffn_fused(q, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, nullptr, nullptr, nullptr, 0, nullptr, 0,
+                                          st);
+        RUN(astts_op_layernorm(q, w.n3_w, w.n3_b, B.n16, 1, rows, C, C, C, 1e-5f, 0.0f, st));
         RUN(linear(B.n16, 1, w.w1, nullptr, B.f16, 1, rows, ASTTS_ACT_GELU));
         return linear(B.f16, 1, w.w2, q, p, 0, rows, ASTTS_ACT_NONE);
     }
@@ -429,8 +430,8 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
         float* fin = const_cast<float*>(up_src);
         RUN(k.mask(fin, B.lens_full, t, C));
         RUN(k.gemm(fin, 0, c.fin_c, nullptr, B.r1, 0, (int64_t)b2 * t, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(astts_op_groupnorm_ex(B.r1, B.lens_full, c.fin_g_w, c.fin_g_b, nullptr, B.r3, 0, b2, t, C, c.groups, 1e-5f, 1, B.gn_ws,
-                                  B.gn_ws_bytes, st));
+        RUN(astts_op_groupnorm(B.r1, B.lens_full, c.fin_g_w, c.fin_g_b, nullptr, B.r3, 0, b2, t, C, c.groups, 1e-5f, 1, B.gn_ws,
+                               B.gn_ws_bytes, st));
         RUN(k.gemm(B.r3, 0, c.fin_p, nullptr, B.d, 0, (int64_t)b2 * t, t, t, 1, 0, ASTTS_ACT_NONE));
         RUN(k.mask(B.d, B.lens_full, t, mel));
         // x += dt * ((1 + r) d_cond - r d_uncond)

@@ -1512,18 +1512,6 @@ size_t astts_knn_workspace_bytes(const astts_knn_t* h, int32_t nq, int32_t k) {
     return make_plan(h, nq, k).total;
 }
 
-int astts_knn_search(astts_knn_t* h, const float* queries, int32_t nq, int32_t k, int64_t* out_idx,
-                     float* out_score, void* workspace, size_t workspace_bytes, int32_t flags,
-                     astts_stream_t stream) {
-    return astts_knn_search_masked(h, queries, nq, k, out_idx, out_score, nullptr, nullptr, 0, workspace, workspace_bytes, flags, stream);
-}
-
-int astts_knn_search_f64(astts_knn_t* h, const float* queries, int32_t nq, int32_t k, int64_t* out_idx,
-                         float* out_score, double* out_score64, void* workspace, size_t workspace_bytes, int32_t flags,
-                         astts_stream_t stream) {
-    return astts_knn_search_masked(h, queries, nq, k, out_idx, out_score, out_score64, nullptr, 0, workspace, workspace_bytes, flags, stream);
-}
-
 }  // extern "C"
 
 namespace {
@@ -1628,8 +1616,8 @@ int knn_search_chunk(astts_knn* h, const KnnPlan& p, const float* queries, int n
             // (built for the HBM-bound small-Q regime) re-reads the query tile from L2 per bank tile.  1 / |b_n| (and L2's
             // constant) are applied by the selection kernel.
             if (n_first)
-                rc = astts_op_gemm_ex(qrow + (size_t)q0 * h->dp, 1, h->plane16, nullptr, nullptr, nullptr, spart, 0, qg, (int32_t)h->n,
-                                      h->dp, h->dp, 1, h->dp, h->nld, 0, qg, qg, 1, 1, 0, ASTTS_ACT_NONE, 1.0f, 0.1f, stream);
+                rc = astts_op_gemm(qrow + (size_t)q0 * h->dp, 1, h->plane16, nullptr, nullptr, nullptr, spart, 0, qg, (int32_t)h->n,
+                                   h->dp, h->dp, 1, h->dp, h->nld, 0, qg, qg, 1, 1, 0, ASTTS_ACT_NONE, 1.0f, 0.1f, nullptr, stream);
             else if (use_blocks)
                 rc = gemm_scan(qrow + (size_t)q0 * h->dp, h->plane16, spart, qg, h->n, h->dp, h->nld, st, h->inv_norm, h->bias, qscale + q0,
                                (float*)(ws + p.off_bmax), p.bm_ld);
@@ -1724,9 +1712,9 @@ int knn_search_chunk(astts_knn* h, const KnnPlan& p, const float* queries, int n
 
 extern "C" {
 
-int astts_knn_search_masked(astts_knn_t* h, const float* queries, int32_t nq, int32_t k, int64_t* out_idx,
-                            float* out_score, double* out_score64, const uint8_t* row_mask, int64_t mask_stride,
-                            void* workspace, size_t workspace_bytes, int32_t flags, astts_stream_t stream) {
+int astts_knn_search(astts_knn_t* h, const float* queries, int32_t nq, int32_t k, int64_t* out_idx,
+                     float* out_score, double* out_score64, const uint8_t* row_mask, int64_t mask_stride,
+                     void* workspace, size_t workspace_bytes, int32_t flags, astts_stream_t stream) {
     ASTTS_REQUIRE(h != nullptr, ASTTS_ERR_INVALID, "astts_knn_search: handle is null");
     ASTTS_REQUIRE(queries && out_idx && out_score, ASTTS_ERR_INVALID, "astts_knn_search: null pointer argument");
     ASTTS_REQUIRE(nq >= 1, ASTTS_ERR_INVALID, "astts_knn_search: nq=%d", nq);

@@ -217,12 +217,12 @@ static int decode_wide(astts_lm* h, const float* logits0, void* const* kv_cache,
     auto gemm = [&](const void* x, int x16, int k, const void* w, const float* bias, const float* res, void* out, int out16, int n, int ldc, int act) {
         if (rows_kernel)
             return astts_op_gemm_rows(x, x16, w, bias, res, out, out16, nullptr, 0, b, n, 0, k, k, ldc, 0, res ? d : 0, act, stream);
-        return astts_op_gemm_ex(x, x16, w, bias, res, nullptr, out, out16, b, n, k, k, 1, k, ldc, res ? d : 0, b, b, 1, 1, 0, act, 1.0f, 0.1f, stream);
+        return astts_op_gemm(x, x16, w, bias, res, nullptr, out, out16, b, n, k, k, 1, k, ldc, res ? d : 0, b, b, 1, 1, 0, act, 1.0f, 0.1f, nullptr, stream);
     };
     // LayerNorm(x) -> fp16 -> projection (optionally with a second destination for the columns >= n_split)
     auto gemm_ln = [&](const float* x, const float* ga, const float* be, const void* w, const float* bias, void* out, int out16, int n, int ldc,
                        int act, void* out2, int n_split, int ldc2) {
-        int rc = astts_op_layernorm_ex(x, ga, be, n16, 1, b, d, d, d, c.eps, stream);
+        int rc = astts_op_layernorm(x, ga, be, n16, 1, b, d, d, d, c.eps, 0.0f, stream);
         if (rc != ASTTS_OK) return rc;
         if (rows_kernel)
             return astts_op_gemm_rows(n16, 1, w, bias, nullptr, out, out16, out2, 1, b, n, n_split, d, d, ldc, ldc2, 0, act, stream);
@@ -244,7 +244,7 @@ static int decode_wide(astts_lm* h, const float* logits0, void* const* kv_cache,
         const int pos = pos0 + s;
         // the token's projected embedding (a row of the load-time table) -> LayerNorm -> ReLU -> * sqrt(d)
         if ((rc = astts_op_embedding(g.embed_table, tok, h1, b, d, d, c.speech_vocab, 1.0f, stream)) != ASTTS_OK) return rc;
-        if ((rc = astts_op_layernorm_relu(h1, g.embed_ln_g, g.embed_ln_b, xa, 0, b, d, d, d, c.eps, sqrtf((float)d), stream)) != ASTTS_OK) return rc;
+        if ((rc = astts_op_layernorm(h1, g.embed_ln_g, g.embed_ln_b, xa, 0, b, d, d, d, c.eps, sqrtf((float)d), stream)) != ASTTS_OK) return rc;
         float* x = xa;
         float* y = xb;
         for (int l = 0; l < c.layers; ++l) {
@@ -252,8 +252,8 @@ static int decode_wide(astts_lm* h, const float* logits0, void* const* kv_cache,
             char* kvc = (char*)kv_cache[l];
             if ((rc = gemm_ln(x, L.n1_g, L.n1_b, L.wqkv, L.bqkv, q, 0, 3 * d, d, ASTTS_ACT_NONE, kvc + (size_t)pos * kv_row * 2, d, 2 * d)) != ASTTS_OK)
                 return rc;
-            rc = astts_op_attn_relpos_ex(q, kvc, kvc + (size_t)d * 2, 1, L.pos, 1, L.bias_u, L.bias_v, nullptr, key_start, ao, b, c.heads, 1, pos + 1,
-                                         b * d, (int32_t)kv_row, b * d, c.pos_ld, d, 2 * d, d, pos, c.pos_center, 1, scale, stream);
+            rc = astts_op_attn_relpos(q, kvc, kvc + (size_t)d * 2, 1, L.pos, 1, L.bias_u, L.bias_v, nullptr, key_start, ao, b, c.heads, 1, pos + 1,
+                                      b * d, (int32_t)kv_row, b * d, c.pos_ld, d, 2 * d, d, pos, c.pos_center, 1, scale, stream);
             if (rc != ASTTS_OK) return rc;
             if ((rc = gemm(ao, 0, d, L.wo, L.bo, x, y, 0, d, d, ASTTS_ACT_NONE)) != ASTTS_OK) return rc;
             if ((rc = gemm_ln(y, L.n2_g, L.n2_b, L.w1, L.b1, ff, 1, c.ffn, c.ffn, ASTTS_ACT_RELU, nullptr, 0, 0)) != ASTTS_OK) return rc;
@@ -307,24 +307,17 @@ size_t astts_lm_workspace_bytes(const astts_lm_t* h, int32_t b) {
 
 // logits0: [B, vocab_out] logits of the last prefix position (from the prefill); kv_cache[l]: fp32 or fp16
 // (cfg.kv_f16) [t_max, B, 2d] time-major, rows [0, pos0) filled by the prefill.  tokens_out: int32 [B, n_steps].
+// Steps [s_begin, s_end) of an n_steps decode: (0, n_steps) is the whole decode; shorter ranges are streaming synthesis (the chain is
+// issued hop by hop, a chunk is rendered while the next hop decodes).  The ranges of one decode are issued in order on ONE stream with
+// the same cache, token buffer and workspace: the workspace carries the logits from one range to the next, tokens_out the sampler's
+// history.
 int astts_lm_decode(astts_lm_t* h, const float* logits0, void* const* kv_cache, const int32_t* key_start, int32_t t_max,
-                    int32_t b, int32_t pos0, int32_t n_steps, const float* uniforms, const int32_t* forced_tokens, int32_t eos_min_steps,
-                    const int32_t* eos_min_rows, int32_t* tokens_out, float* logits_out, void* workspace, size_t workspace_bytes,
-                    astts_stream_t stream) {
-    return astts_lm_decode_range(h, logits0, kv_cache, key_start, t_max, b, pos0, n_steps, 0, n_steps, uniforms, forced_tokens, eos_min_steps,
-                                 eos_min_rows, tokens_out, logits_out, workspace, workspace_bytes, stream);
-}
-
-// Steps [s_begin, s_end) of an n_steps decode (streaming synthesis: the chain is issued hop by hop, a chunk is rendered while the next
-// hop decodes).  The ranges of one decode are issued in order on ONE stream with the same cache, token buffer and workspace: the
-// workspace carries the logits from one range to the next, tokens_out the sampler's history.  Range (0, n_steps) = astts_lm_decode.
-int astts_lm_decode_range(astts_lm_t* h, const float* logits0, void* const* kv_cache, const int32_t* key_start, int32_t t_max,
-                          int32_t b, int32_t pos0, int32_t n_steps, int32_t s_begin, int32_t s_end, const float* uniforms,
-                          const int32_t* forced_tokens, int32_t eos_min_steps, const int32_t* eos_min_rows, int32_t* tokens_out,
-                          float* logits_out, void* workspace, size_t workspace_bytes, astts_stream_t stream) {
+                    int32_t b, int32_t pos0, int32_t n_steps, int32_t s_begin, int32_t s_end, const float* uniforms,
+                    const int32_t* forced_tokens, int32_t eos_min_steps, const int32_t* eos_min_rows, int32_t* tokens_out,
+                    float* logits_out, void* workspace, size_t workspace_bytes, astts_stream_t stream) {
     ASTTS_REQUIRE(h && logits0 && kv_cache && uniforms && tokens_out && workspace, ASTTS_ERR_INVALID,
                   "astts_lm_decode: null argument");
-    ASTTS_REQUIRE(s_begin >= 0 && s_begin < s_end && s_end <= n_steps, ASTTS_ERR_INVALID, "astts_lm_decode_range: steps [%d, %d) of %d", s_begin,
+    ASTTS_REQUIRE(s_begin >= 0 && s_begin < s_end && s_end <= n_steps, ASTTS_ERR_INVALID, "astts_lm_decode: steps [%d, %d) of %d", s_begin,
                   s_end, n_steps);
     ASTTS_REQUIRE(b >= 1 && b <= ASTTS_LM_MAX_ROWS, ASTTS_ERR_INVALID, "astts_lm_decode: b=%d (1..%d per call)", b, ASTTS_LM_MAX_ROWS);
     ASTTS_REQUIRE(n_steps >= 1 && pos0 >= 1 && pos0 + n_steps - 1 <= t_max, ASTTS_ERR_INVALID,
@@ -385,10 +378,10 @@ int astts_lm_decode_range(astts_lm_t* h, const float* logits0, void* const* kv_c
         if (s + 1 == n_steps) break;
         const int pos = pos0 + s;
         // embed: speech_embedding[tok] -> Linear -> LayerNorm -> ReLU * sqrt(d)
-        rc = astts_op_gemm_fused_ws(g.speech_emb, tok, nullptr, nullptr, 0.f, g.embed_w, g.embed_b, nullptr, h1, nullptr, 0, b, d, 0,
-                                 d, dpad, d, d, 0, 0, ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
+        rc = astts_op_gemm_fused(g.speech_emb, tok, nullptr, nullptr, 0.f, g.embed_w, g.embed_b, nullptr, h1, nullptr, 0, b, d, 0,
+                              d, dpad, d, d, 0, 0, ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
         if (rc != ASTTS_OK) return rc;
-        rc = astts_op_layernorm_relu(h1, g.embed_ln_g, g.embed_ln_b, h0, 0, b, d, d, d, c.eps, sqrtf((float)d), st);
+        rc = astts_op_layernorm(h1, g.embed_ln_g, g.embed_ln_b, h0, 0, b, d, d, d, c.eps, sqrtf((float)d), st);
         if (rc != ASTTS_OK) return rc;
         float* x = h0;
         float* y = h1;
@@ -397,27 +390,27 @@ int astts_lm_decode_range(astts_lm_t* h, const float* logits0, void* const* kv_c
             char* kvc = (char*)kv_cache[l];
             const size_t esz = c.kv_f16 ? 2 : 4;
             // LN1 + QKV; K|V land in cache row `pos`
-            rc = astts_op_gemm_fused_ws(x, nullptr, L.n1_g, L.n1_b, c.eps, L.wqkv, L.bqkv, nullptr, q,
-                                     kvc + (size_t)pos * kv_row * esz, c.kv_f16, b, 3 * d, d, d, dpad, d, d, 2 * d, 0,
-                                     ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
+            rc = astts_op_gemm_fused(x, nullptr, L.n1_g, L.n1_b, c.eps, L.wqkv, L.bqkv, nullptr, q,
+                                  kvc + (size_t)pos * kv_row * esz, c.kv_f16, b, 3 * d, d, d, dpad, d, d, 2 * d, 0,
+                                  ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
             if (rc != ASTTS_OK) return rc;
-            rc = astts_op_attn_relpos_ex(q, kvc, kvc + (size_t)d * esz, c.kv_f16, L.pos, c.pos_f16, L.bias_u, L.bias_v, /*lens: every row has pos + 1 keys*/ nullptr, key_start, ao, b,
-                                         c.heads, 1, pos + 1, /*ldq*/ b * d, /*ldk*/ (int32_t)kv_row, /*ldo*/ b * d, c.pos_ld,
-                                         /*q_bs*/ d, /*k_bs*/ 2 * d, /*o_bs*/ d, pos, c.pos_center, 1, scale, st);
+            rc = astts_op_attn_relpos(q, kvc, kvc + (size_t)d * esz, c.kv_f16, L.pos, c.pos_f16, L.bias_u, L.bias_v, /*lens: every row has pos + 1 keys*/ nullptr, key_start, ao, b,
+                                      c.heads, 1, pos + 1, /*ldq*/ b * d, /*ldk*/ (int32_t)kv_row, /*ldo*/ b * d, c.pos_ld,
+                                      /*q_bs*/ d, /*k_bs*/ 2 * d, /*o_bs*/ d, pos, c.pos_center, 1, scale, st);
             if (rc != ASTTS_OK) return rc;
-            rc = astts_op_gemm_fused_ws(ao, nullptr, nullptr, nullptr, 0.f, L.wo, L.bo, x, y, nullptr, 0, b, d, 0, d, dpad, d, d, 0, d,
-                                     ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
+            rc = astts_op_gemm_fused(ao, nullptr, nullptr, nullptr, 0.f, L.wo, L.bo, x, y, nullptr, 0, b, d, 0, d, dpad, d, d, 0, d,
+                                  ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
             if (rc != ASTTS_OK) return rc;
-            rc = astts_op_gemm_fused_ws(y, nullptr, L.n2_g, L.n2_b, c.eps, L.w1, L.b1, nullptr, ff, nullptr, 0, b, c.ffn, 0, d, dpad, d,
-                                     c.ffn, 0, 0, ASTTS_ACT_RELU, 1.f, 0.f, skw, skw_bytes, st);
+            rc = astts_op_gemm_fused(y, nullptr, L.n2_g, L.n2_b, c.eps, L.w1, L.b1, nullptr, ff, nullptr, 0, b, c.ffn, 0, d, dpad, d,
+                                  c.ffn, 0, 0, ASTTS_ACT_RELU, 1.f, 0.f, skw, skw_bytes, st);
             if (rc != ASTTS_OK) return rc;
-            rc = astts_op_gemm_fused_ws(ff, nullptr, nullptr, nullptr, 0.f, L.w2, L.b2, y, x, nullptr, 0, b, d, 0, c.ffn, fpad, c.ffn, d,
-                                     0, d, ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
+            rc = astts_op_gemm_fused(ff, nullptr, nullptr, nullptr, 0.f, L.w2, L.b2, y, x, nullptr, 0, b, d, 0, c.ffn, fpad, c.ffn, d,
+                                  0, d, ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
             if (rc != ASTTS_OK) return rc;
         }
         // after_norm + output head
-        rc = astts_op_gemm_fused_ws(x, nullptr, g.after_g, g.after_b, c.eps, g.head_w, g.head_b, nullptr, lg, nullptr, 0, b, c.vocab_out,
-                                 0, d, dpad, d, c.vocab_out, 0, 0, ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
+        rc = astts_op_gemm_fused(x, nullptr, g.after_g, g.after_b, c.eps, g.head_w, g.head_b, nullptr, lg, nullptr, 0, b, c.vocab_out,
+                              0, d, dpad, d, c.vocab_out, 0, 0, ASTTS_ACT_NONE, 1.f, 0.f, skw, skw_bytes, st);
         if (rc != ASTTS_OK) return rc;
         cur = lg;
     }

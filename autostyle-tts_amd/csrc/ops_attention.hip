@@ -800,11 +800,11 @@ using namespace astts;
 
 extern "C" {
 
-int astts_op_attn_relpos_ex(const float* q, const void* k, const void* v, int32_t kv_f16, const void* pos, int32_t pos_f16,
-                            const float* bias_u, const float* bias_v, const int32_t* lens, const int32_t* key_start, float* out,
-                            int32_t b, int32_t h, int32_t tq, int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp,
-                            int64_t q_bs, int64_t k_bs, int64_t o_bs, int32_t q_pos0, int32_t pos_center, int32_t causal,
-                            float scale, astts_stream_t stream) {
+int astts_op_attn_relpos(const float* q, const void* k, const void* v, int32_t kv_f16, const void* pos, int32_t pos_f16,
+                         const float* bias_u, const float* bias_v, const int32_t* lens, const int32_t* key_start, float* out,
+                         int32_t b, int32_t h, int32_t tq, int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp,
+                         int64_t q_bs, int64_t k_bs, int64_t o_bs, int32_t q_pos0, int32_t pos_center, int32_t causal,
+                         float scale, astts_stream_t stream) {
     ASTTS_REQUIRE(q && k && v && pos && bias_u && bias_v && out, ASTTS_ERR_INVALID, "astts_op_attn_relpos: null pointer");
     ASTTS_REQUIRE(b >= 1 && h >= 1 && tq >= 1 && tk >= 1, ASTTS_ERR_INVALID, "astts_op_attn_relpos: bad shape");
     ASTTS_REQUIRE(q_pos0 + tq - 1 <= pos_center && tk - 1 <= pos_center + q_pos0, ASTTS_ERR_INVALID,
@@ -871,18 +871,9 @@ int astts_op_attn_relpos_ex(const float* q, const void* k, const void* v, int32_
     return ASTTS_OK;
 }
 
-int astts_op_attn_relpos(const float* q, const float* k, const float* v, const float* pos, const float* bias_u,
-                         const float* bias_v, const int32_t* lens, float* out, int32_t b, int32_t h, int32_t tq,
-                         int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp, int64_t q_bs, int64_t k_bs,
-                         int64_t o_bs, int32_t q_pos0, int32_t pos_center, int32_t causal, float scale,
-                         astts_stream_t stream) {
-    return astts_op_attn_relpos_ex(q, k, v, 0, pos, 0, bias_u, bias_v, lens, nullptr, out, b, h, tq, tk, ldq, ldk, ldo, ldp, q_bs, k_bs,
-                                   o_bs, q_pos0, pos_center, causal, scale, stream);
-}
-
-int astts_op_attn_mha_ex(const void* q, const void* k, const void* v, int32_t in_f16, const int32_t* lens, void* out,
-                         int32_t out_f16, int32_t b, int32_t h, int32_t t, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
-                         astts_stream_t stream) {
+int astts_op_attn_mha(const void* q, const void* k, const void* v, int32_t in_f16, const int32_t* lens, void* out,
+                      int32_t out_f16, int32_t b, int32_t h, int32_t t, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
+                      astts_stream_t stream) {
     ASTTS_REQUIRE(q && k && v && out, ASTTS_ERR_INVALID, "astts_op_attn_mha: null pointer");
     ASTTS_REQUIRE(b >= 1 && h >= 1 && t >= 1, ASTTS_ERR_INVALID, "astts_op_attn_mha: bad shape");
     const int al = in_f16 ? 7 : 3;
@@ -904,11 +895,6 @@ int astts_op_attn_mha_ex(const void* q, const void* k, const void* v, int32_t in
     if (prof) prof_end(ASTTS_PROF_ATTN_FLASH, st);
     ASTTS_CHECK_LAUNCH();
     return ASTTS_OK;
-}
-
-int astts_op_attn_mha(const float* q, const float* k, const float* v, const int32_t* lens, float* out, int32_t b,
-                      int32_t h, int32_t t, int32_t ldq, int32_t ldk, int32_t ldo, float scale, astts_stream_t stream) {
-    return astts_op_attn_mha_ex(q, k, v, 0, lens, out, 0, b, h, t, ldq, ldk, ldo, scale, stream);
 }
 
 }  // extern "C"

@@ -681,11 +681,7 @@ int astts_op_nsf_source(const float* f0, const float* phase0, const float* noise
     return ASTTS_OK;
 }
 
-int astts_op_stft16(const float* x, float* y, int32_t b, int64_t n_samples, astts_stream_t stream) {
-    return astts_op_stft16_lens(x, y, b, n_samples, nullptr, stream);
-}
-
-int astts_op_stft16_lens(const float* x, float* y, int32_t b, int64_t n_samples, const int32_t* lens, astts_stream_t stream) {
+int astts_op_stft16(const float* x, float* y, int32_t b, int64_t n_samples, const int32_t* lens, astts_stream_t stream) {
     ASTTS_REQUIRE(x && y && b >= 1 && n_samples >= 16 && n_samples % 4 == 0, ASTTS_ERR_INVALID, "astts_op_stft16: bad argument");
     const int64_t F = n_samples / 4 + 1;
     hipLaunchKernelGGL(stft16, dim3(grid_for_a((int64_t)b * F)), dim3(256), 0, (hipStream_t)stream, x, y, b, n_samples, F, lens);
@@ -693,13 +689,8 @@ int astts_op_stft16_lens(const float* x, float* y, int32_t b, int64_t n_samples,
     return ASTTS_OK;
 }
 
-int astts_op_istft16(const float* y, float* wav, int32_t b, int64_t frames, float mag_clip, float audio_limit,
+int astts_op_istft16(const float* y, float* wav, int32_t b, int64_t frames, float mag_clip, float audio_limit, const int32_t* frame_lens,
                      astts_stream_t stream) {
-    return astts_op_istft16_lens(y, wav, b, frames, mag_clip, audio_limit, nullptr, stream);
-}
-
-int astts_op_istft16_lens(const float* y, float* wav, int32_t b, int64_t frames, float mag_clip, float audio_limit, const int32_t* frame_lens,
-                          astts_stream_t stream) {
     ASTTS_REQUIRE(y && wav && b >= 1 && frames >= 2, ASTTS_ERR_INVALID, "astts_op_istft16: bad argument");
     hipLaunchKernelGGL(istft16, dim3(grid_for_a((int64_t)b * 4 * (frames - 1))), dim3(256), 0, (hipStream_t)stream, y,
                        wav, b, frames, mag_clip, audio_limit, frame_lens);

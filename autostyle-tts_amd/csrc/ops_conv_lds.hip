@@ -255,13 +255,7 @@ int astts_op_conv1d_snake_supported(int32_t c, int32_t taps, int32_t dil) {
 
 int astts_op_conv1d_snake(const void* x, int32_t x_f16, const float* alpha, const void* w_frag_f16, const float* bias, const float* res,
                           void* y, int32_t y_f16, float* acc, float acc_scale, int32_t acc_add, int32_t b, int32_t l, int32_t c,
-                          int32_t taps, int32_t dil, astts_stream_t stream) {
-    return astts_op_conv1d_snake_lens(x, x_f16, alpha, w_frag_f16, bias, res, y, y_f16, acc, acc_scale, acc_add, b, l, c, taps, dil, nullptr, stream);
-}
-
-int astts_op_conv1d_snake_lens(const void* x, int32_t x_f16, const float* alpha, const void* w_frag_f16, const float* bias, const float* res,
-                               void* y, int32_t y_f16, float* acc, float acc_scale, int32_t acc_add, int32_t b, int32_t l, int32_t c,
-                               int32_t taps, int32_t dil, const int32_t* lens, astts_stream_t stream) {
+                          int32_t taps, int32_t dil, const int32_t* lens, astts_stream_t stream) {
     ASTTS_REQUIRE(x && w_frag_f16 && (y || acc), ASTTS_ERR_INVALID, "astts_op_conv1d_snake: null pointer");
     ASTTS_REQUIRE(astts_op_conv1d_snake_supported(c, taps, dil), ASTTS_ERR_UNSUPPORTED,
                   "astts_op_conv1d_snake: c=%d taps=%d dil=%d (c 128 or 256, odd taps, halo <= 25)", c, taps, dil);

@@ -1541,38 +1541,12 @@ int astts_op_pack_weight(const float* src, void* dst_f16, int32_t n, int32_t tap
     return ASTTS_OK;
 }
 
-int astts_op_gemm(const float* x, const void* w_f16, const float* bias, const float* residual,
-                  const float* row_scale, float* out, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
+int astts_op_gemm(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
+                  const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
                   int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                  int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope,
+                  int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
                   astts_stream_t stream) {
-    const int rc = check_gemm_args("astts_op_gemm", x, w_f16, out, m, n, cin, cin_pad, taps, t_in, t_out, stride, dil, act);
-    if (rc != ASTTS_OK) return rc;
-    GemmArgs a{x, (const _Float16*)w_f16, bias, residual, row_scale, out, m, n, cin, cin_pad, taps,
-               lda, ldc, ldr, t_in, t_out, stride, dil, pad, act, alpha, slope,
-               nullptr, nullptr, nullptr, 0.0f, nullptr, 0, 0, 0, 0, 0};
-    return launch_gemm(a, (hipStream_t)stream);
-}
-
-int astts_op_gemm_ex(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
-                     const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
-                     int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                     int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope,
-                     astts_stream_t stream) {
-    const int rc = check_gemm_args("astts_op_gemm_ex", (const float*)x, w_f16, (float*)out, m, n, cin, cin_pad, taps, t_in, t_out, stride, dil, act);
-    if (rc != ASTTS_OK) return rc;
-    GemmArgs a{(const float*)x, (const _Float16*)w_f16, bias, residual, row_scale, (float*)out, m, n, cin, cin_pad, taps,
-               lda, ldc, ldr, t_in, t_out, stride, dil, pad, act, alpha, slope,
-               nullptr, nullptr, nullptr, 0.0f, nullptr, 0, 0, x_f16 ? 1 : 0, out_f16 ? 1 : 0, 0};
-    return launch_gemm(a, (hipStream_t)stream);
-}
-
-int astts_op_gemm_lens(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
-                       const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
-                       int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                       int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
-                       astts_stream_t stream) {
-    const int rc = check_gemm_args("astts_op_gemm_lens", (const float*)x, w_f16, (float*)out, m, n, cin, cin_pad, taps, t_in, t_out, stride, dil, act);
+    const int rc = check_gemm_args("astts_op_gemm", (const float*)x, w_f16, (float*)out, m, n, cin, cin_pad, taps, t_in, t_out, stride, dil, act);
     if (rc != ASTTS_OK) return rc;
     GemmArgs a{(const float*)x, (const _Float16*)w_f16, bias, residual, row_scale, (float*)out, m, n, cin, cin_pad, taps,
                lda, ldc, ldr, t_in, t_out, stride, dil, pad, act, alpha, slope,
@@ -1645,11 +1619,11 @@ size_t astts_op_gemm_fused_workspace_bytes(void) {
     return 1024 + (size_t)128 * 4 * 512 * sizeof(float);      // arrival counters + [128 column blocks][4 slices][512] partial sums
 }
 
-int astts_op_gemm_fused_ws(const float* x, const int32_t* gather, const float* ln_gamma, const float* ln_beta, float ln_eps,
-                           const void* w_f16, const float* bias, const float* residual, float* out, void* out2, int32_t out2_f16,
-                           int32_t m, int32_t n, int32_t n_split, int32_t cin, int32_t cin_pad, int32_t lda, int32_t ldc,
-                           int32_t ldc2, int32_t ldr, int32_t act, float alpha, float slope, void* workspace, size_t workspace_bytes,
-                           astts_stream_t stream) {
+int astts_op_gemm_fused(const float* x, const int32_t* gather, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                        const void* w_f16, const float* bias, const float* residual, float* out, void* out2, int32_t out2_f16,
+                        int32_t m, int32_t n, int32_t n_split, int32_t cin, int32_t cin_pad, int32_t lda, int32_t ldc,
+                        int32_t ldc2, int32_t ldr, int32_t act, float alpha, float slope, void* workspace, size_t workspace_bytes,
+                        astts_stream_t stream) {
     const int rc = check_gemm_args("astts_op_gemm_fused", x, w_f16, out, m, n, cin, cin_pad, 1, 1, 1, 1, 1, act);
     if (rc != ASTTS_OK) return rc;
     ASTTS_REQUIRE(m <= 32, ASTTS_ERR_INVALID, "astts_op_gemm_fused: m=%d > 32", m);
@@ -1662,14 +1636,6 @@ int astts_op_gemm_fused_ws(const float* x, const int32_t* gather, const float* l
                gather, ln_gamma, ln_beta, ln_eps, (float*)out2, ldc2, n_split, 0, 0, out2_f16 ? 1 : 0,
                workspace ? reinterpret_cast<float*>((char*)workspace + 1024) : nullptr, reinterpret_cast<unsigned*>(workspace), 0};
     return launch_gemm(a, (hipStream_t)stream);
-}
-
-int astts_op_gemm_fused(const float* x, const int32_t* gather, const float* ln_gamma, const float* ln_beta, float ln_eps,
-                        const void* w_f16, const float* bias, const float* residual, float* out, void* out2, int32_t out2_f16,
-                        int32_t m, int32_t n, int32_t n_split, int32_t cin, int32_t cin_pad, int32_t lda, int32_t ldc,
-                        int32_t ldc2, int32_t ldr, int32_t act, float alpha, float slope, astts_stream_t stream) {
-    return astts_op_gemm_fused_ws(x, gather, ln_gamma, ln_beta, ln_eps, w_f16, bias, residual, out, out2, out2_f16, m, n, n_split, cin,
-                                  cin_pad, lda, ldc, ldc2, ldr, act, alpha, slope, nullptr, 0, stream);
 }
 
 }  // extern "C"

@@ -464,8 +464,8 @@ static inline int grid_for(int64_t total) {
 
 extern "C" {
 
-int astts_op_layernorm_relu(const float* x, const float* gamma, const float* beta, void* y, int32_t out_f16, int64_t rows,
-                            int32_t c, int32_t ldx, int32_t ldy, float eps, float relu_scale, astts_stream_t stream) {
+int astts_op_layernorm(const float* x, const float* gamma, const float* beta, void* y, int32_t out_f16, int64_t rows,
+                       int32_t c, int32_t ldx, int32_t ldy, float eps, float relu_scale, astts_stream_t stream) {
     ASTTS_REQUIRE(x && gamma && beta && y && rows >= 1 && c >= 1 && relu_scale >= 0.0f, ASTTS_ERR_INVALID, "astts_op_layernorm: bad argument");
     if (out_f16)
         hipLaunchKernelGGL((layernorm_rows<_Float16>), dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, x,
@@ -477,29 +477,13 @@ int astts_op_layernorm_relu(const float* x, const float* gamma, const float* bet
     return ASTTS_OK;
 }
 
-int astts_op_layernorm_ex(const float* x, const float* gamma, const float* beta, void* y, int32_t out_f16, int64_t rows,
-                          int32_t c, int32_t ldx, int32_t ldy, float eps, astts_stream_t stream) {
-    return astts_op_layernorm_relu(x, gamma, beta, y, out_f16, rows, c, ldx, ldy, eps, 0.0f, stream);
-}
-
-int astts_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int32_t c,
-                       int32_t ldx, int32_t ldy, float eps, astts_stream_t stream) {
-    return astts_op_layernorm_ex(x, gamma, beta, y, 0, rows, c, ldx, ldy, eps, stream);
-}
-
 size_t astts_op_groupnorm_workspace_bytes(int32_t b, int32_t t, int32_t groups) {
     return (size_t)b * cdiv(t, GN_ROWS) * groups * 2 * sizeof(float);
 }
 
 int astts_op_groupnorm(const float* x, const int32_t* lens, const float* gamma, const float* beta,
-                       const float* add_bc, float* y, int32_t b, int32_t t, int32_t c, int32_t groups, float eps,
-                       int32_t act_mish, void* workspace, size_t workspace_bytes, astts_stream_t stream) {
-    return astts_op_groupnorm_ex(x, lens, gamma, beta, add_bc, y, 0, b, t, c, groups, eps, act_mish, workspace, workspace_bytes, stream);
-}
-
-int astts_op_groupnorm_ex(const float* x, const int32_t* lens, const float* gamma, const float* beta,
-                          const float* add_bc, void* y, int32_t out_f16, int32_t b, int32_t t, int32_t c, int32_t groups,
-                          float eps, int32_t act_mish, void* workspace, size_t workspace_bytes, astts_stream_t stream) {
+                       const float* add_bc, void* y, int32_t out_f16, int32_t b, int32_t t, int32_t c, int32_t groups,
+                       float eps, int32_t act_mish, void* workspace, size_t workspace_bytes, astts_stream_t stream) {
     ASTTS_REQUIRE(x && gamma && beta && y && workspace, ASTTS_ERR_INVALID, "astts_op_groupnorm: null pointer");
     ASTTS_REQUIRE(b >= 1 && t >= 1 && c >= 1 && groups >= 1 && c % groups == 0 && groups <= 256 && c <= 8192,
                   ASTTS_ERR_INVALID, "astts_op_groupnorm: bad shape b=%d t=%d c=%d groups=%d", b, t, c, groups);
@@ -561,18 +545,13 @@ int astts_op_embedding(const float* table, const int32_t* ids, float* y, int64_t
     return ASTTS_OK;
 }
 
-int astts_op_interp_linear_ex(const float* x, float* y, int32_t b, int32_t t_in, int32_t t_out, int32_t c,
-                              const int32_t* in_lens, const int32_t* out_lens, astts_stream_t stream) {
+int astts_op_interp_linear(const float* x, float* y, int32_t b, int32_t t_in, int32_t t_out, int32_t c,
+                           const int32_t* in_lens, const int32_t* out_lens, astts_stream_t stream) {
     ASTTS_REQUIRE(x && y && b >= 1 && t_in >= 1 && t_out >= 1 && c >= 1, ASTTS_ERR_INVALID, "astts_op_interp_linear: bad argument");
     hipLaunchKernelGGL(interp_linear_rows, dim3(grid_for((int64_t)b * t_out * c)), dim3(256), 0, (hipStream_t)stream, x,
                        y, b, t_in, t_out, c, in_lens, out_lens);
     ASTTS_CHECK_LAUNCH();
     return ASTTS_OK;
-}
-
-int astts_op_interp_linear(const float* x, float* y, int32_t b, int32_t t_in, int32_t t_out, int32_t c,
-                           astts_stream_t stream) {
-    return astts_op_interp_linear_ex(x, y, b, t_in, t_out, c, nullptr, nullptr, stream);
 }
 
 int astts_op_time_embedding(const float* t, float* y, int32_t b, int32_t dim, float scale, astts_stream_t stream) {

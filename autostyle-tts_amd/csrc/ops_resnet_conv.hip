@@ -337,15 +337,7 @@ int astts_op_resnet_conv_supported(int32_t cin, int32_t cout, int32_t groups, in
 int astts_op_resnet_conv(const float* x, const void* w_frag_f16, const float* bias, float* out, const float* in_stats, const float* in_gamma,
                          const float* in_beta, const float* in_add, const float* res, const float* res_stats, const float* res_gamma,
                          const float* res_beta, float* out_stats, const int32_t* lens, int32_t b, int32_t t, int32_t cin, int32_t taps,
-                         float eps, astts_stream_t stream) {
-    return astts_op_resnet_conv_pf(x, w_frag_f16, bias, out, in_stats, in_gamma, in_beta, in_add, res, res_stats, res_gamma, res_beta, out_stats,
-                                   lens, b, t, cin, taps, eps, nullptr, 0, stream);
-}
-
-int astts_op_resnet_conv_pf(const float* x, const void* w_frag_f16, const float* bias, float* out, const float* in_stats, const float* in_gamma,
-                            const float* in_beta, const float* in_add, const float* res, const float* res_stats, const float* res_gamma,
-                            const float* res_beta, float* out_stats, const int32_t* lens, int32_t b, int32_t t, int32_t cin, int32_t taps,
-                            float eps, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
+                         float eps, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
     ASTTS_REQUIRE(x && w_frag_f16 && out && x != out, ASTTS_ERR_INVALID, "astts_op_resnet_conv: null / aliased pointer");
     ASTTS_REQUIRE(astts_op_resnet_conv_supported(cin, RC_C, 8, taps), ASTTS_ERR_UNSUPPORTED,
                   "astts_op_resnet_conv: cin=%d taps=%d (256 or 512 input channels, 1 or 3 taps)", cin, taps);

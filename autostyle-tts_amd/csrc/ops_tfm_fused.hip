@@ -780,14 +780,7 @@ int astts_op_tfm_ffn_fused_supported(int32_t c, int32_t hidden) {
 
 int astts_op_tfm_ffn_fused(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
                            int64_t m, int32_t c, int32_t hidden, float eps, const void* attn_f16, const void* wo_frag_f16,
-                           const float* bo, int32_t k0, astts_stream_t stream) {
-    return astts_op_tfm_ffn_fused_pf(x, w1_frag_f16, b1, w2_frag_f16, b2, out, m, c, hidden, eps, attn_f16, wo_frag_f16, bo, k0, nullptr, 0,
-                                     stream);
-}
-
-int astts_op_tfm_ffn_fused_pf(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
-                              int64_t m, int32_t c, int32_t hidden, float eps, const void* attn_f16, const void* wo_frag_f16,
-                              const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
+                           const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
     ASTTS_REQUIRE(x && w1_frag_f16 && w2_frag_f16 && out, ASTTS_ERR_INVALID, "astts_op_tfm_ffn_fused: null pointer");
     ASTTS_REQUIRE(astts_op_tfm_ffn_fused_supported(c, hidden), ASTTS_ERR_UNSUPPORTED,
                   "astts_op_tfm_ffn_fused: c=%d hidden=%d (channels 256, hidden a multiple of 256 <= 4096)", c, hidden);
@@ -828,14 +821,9 @@ int astts_op_tfm_attn_fused_supported(int32_t c, int32_t heads, int32_t t) {
 }
 
 int astts_op_tfm_attn_fused(const float* x, const void* wqkv_frag_f16, const float* bias, const int32_t* lens, void* out_f16, int32_t b,
-                            int32_t heads, int32_t t, int32_t c, float eps, float scale, astts_stream_t stream) {
-    return astts_op_tfm_attn_fused_pf(x, wqkv_frag_f16, bias, lens, out_f16, b, heads, t, c, eps, scale, nullptr, nullptr, 0, stream);
-}
-
-int astts_op_tfm_attn_fused_pf(const float* x, const void* wqkv_frag_f16, const float* bias, const int32_t* lens, void* out_f16, int32_t b,
-                               int32_t heads, int32_t t, int32_t c, float eps, float scale, const void* const* pf_ptrs,
-                               const uint32_t* pf_bytes, int32_t n_pf, astts_stream_t stream) {
-    ASTTS_REQUIRE(n_pf >= 0 && n_pf <= 3 && (n_pf == 0 || (pf_ptrs && pf_bytes)), ASTTS_ERR_INVALID, "astts_op_tfm_attn_fused_pf: n_pf=%d", n_pf);
+                            int32_t heads, int32_t t, int32_t c, float eps, float scale, const void* const* pf_ptrs,
+                            const uint32_t* pf_bytes, int32_t n_pf, astts_stream_t stream) {
+    ASTTS_REQUIRE(n_pf >= 0 && n_pf <= 3 && (n_pf == 0 || (pf_ptrs && pf_bytes)), ASTTS_ERR_INVALID, "astts_op_tfm_attn_fused: n_pf=%d", n_pf);
     ASTTS_REQUIRE(x && wqkv_frag_f16 && out_f16, ASTTS_ERR_INVALID, "astts_op_tfm_attn_fused: null pointer");
     ASTTS_REQUIRE(astts_op_tfm_attn_fused_supported(c, heads, t), ASTTS_ERR_UNSUPPORTED,
                   "astts_op_tfm_attn_fused: c=%d heads=%d t=%d (channels 256, t <= %d)", c, heads, t, TF_MAX_T);

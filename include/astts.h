@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTTS_ABI_VERSION 5
+#define ASTTS_ABI_VERSION 6
 
 #define ASTTS_OK 0
 #define ASTTS_ERR_INVALID (-1)     /* bad argument (null pointer, size, dtype, k, ...)            */
@@ -104,26 +104,19 @@ int astts_knn_destroy(astts_knn_t* h);
 int astts_knn_info(const astts_knn_t* h, int64_t* n, int32_t* d, int32_t* scan_plane_exact);
 /* Bytes of workspace astts_knn_search needs for up to `nq` queries and `k` hits. */
 size_t astts_knn_workspace_bytes(const astts_knn_t* h, int32_t nq, int32_t k);
-/* queries: fp32 [nq,d] device.  out_idx: int64 [nq,k], out_score: fp32 [nq,k] (cosine
- * similarity, larger = closer; rows beyond min(k,n) hits get idx -1 / score -inf).
- * workspace: 256-byte aligned device memory of at least astts_knn_workspace_bytes(h,nq,k). */
+/* queries: fp32 [nq,d] device.  out_idx: int64 [nq,k], out_score: fp32 [nq,k].  Hits are ordered closest first under the
+ * handle's metric (COSINE / IP: score descending; L2: squared distance ascending), ties by row index ascending; out_score holds
+ * the metric's own value; rows beyond the hits that exist get idx -1 and score -inf (+inf for L2).  1 <= k <= ASTTS_KNN_MAX_K.
+ * workspace: 256-byte aligned device memory of at least astts_knn_workspace_bytes(h,nq,k).  Optional (NULL = absent):
+ *   out_score64  fp64 [nq,k], the same scores unrounded: what a bank-SHARDED search merges on -- W ranks each return the top-k
+ *                of their rows, and the k-way merge must order candidates of different ranks exactly as the oracle orders them
+ *                (fp64 score descending, global row ascending); fp32-rounded scores could tie where fp64 do not.
+ *   row_mask     uint8 [n] when mask_stride == 0, else one row of mask_stride >= n bytes per query: restricts the search to the
+ *                rows whose byte is non-zero -- a Milvus `filter` expression evaluated by the host (milvus/search_json.py:246-252
+ *                passes filter=None). */
 int astts_knn_search(astts_knn_t* h, const float* queries, int32_t nq, int32_t k,
-                     int64_t* out_idx, float* out_score, void* workspace, size_t workspace_bytes,
-                     int32_t flags, astts_stream_t stream);
-/* The same search with the fp64 cosines as well (out_score64 fp64 [nq,k], may be NULL): what a bank-SHARDED search merges
- * on -- W ranks each return the top-k of their rows, and the k-way merge must order candidates of different ranks exactly
- * as the oracle orders them (fp64 score descending, global row ascending); fp32-rounded scores could tie where fp64 do not. */
-int astts_knn_search_f64(astts_knn_t* h, const float* queries, int32_t nq, int32_t k,
-                         int64_t* out_idx, float* out_score, double* out_score64, void* workspace, size_t workspace_bytes,
-                         int32_t flags, astts_stream_t stream);
-/* The general form: `row_mask` (uint8 [n] when mask_stride == 0, else one row of mask_stride >= n bytes per query; NULL = every
- * row) restricts the search to the rows whose byte is non-zero -- a Milvus `filter` expression evaluated by the host
- * (milvus/search_json.py:246-252 passes filter=None).  Hits are ordered closest first under the handle's metric
- * (COSINE / IP: score descending; L2: squared distance ascending), ties by row index ascending; out_score / out_score64 hold the
- * metric's own value; rows beyond the hits that exist get idx -1 and score -inf (+inf for L2).  1 <= k <= ASTTS_KNN_MAX_K. */
-int astts_knn_search_masked(astts_knn_t* h, const float* queries, int32_t nq, int32_t k,
-                            int64_t* out_idx, float* out_score, double* out_score64, const uint8_t* row_mask, int64_t mask_stride,
-                            void* workspace, size_t workspace_bytes, int32_t flags, astts_stream_t stream);
+                     int64_t* out_idx, float* out_score, double* out_score64, const uint8_t* row_mask, int64_t mask_stride,
+                     void* workspace, size_t workspace_bytes, int32_t flags, astts_stream_t stream);
 /* Number of queries of the last search on `workspace` that took the exact-scan fallback.
  * Copies one word back and synchronises `stream` (diagnostics; not a launch-path call). */
 int astts_knn_last_fallbacks(const astts_knn_t* h, const void* workspace, astts_stream_t stream,
@@ -157,28 +150,18 @@ int astts_op_pack_weight(const float* src, void* dst_f16, int32_t n, int32_t tap
                          int32_t n_pad, int32_t cin_pad, astts_stream_t stream);
 /* Implicit GEMM (nn.Linear / nn.Conv1d / phase-decomposed nn.ConvTranspose1d):
  *   out[m, n] = act(sum_{tap,c} x[b*t_in + t*stride + tap*dil - pad, c] * w[n, tap, c] + bias[n]) * alpha
- *               * row_scale[m] + residual[m, n],      m = b*t_out + t, zero outside [0, t_in). */
-int astts_op_gemm(const float* x, const void* w_f16, const float* bias, const float* residual,
-                  const float* row_scale, float* out, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
-                  int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                  int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope,
-                  astts_stream_t stream);
-/* Same contraction with fp16 activation input and/or output (x_f16 / out_f16 != 0; lda / ldc then count halfs).
- * A producer whose only consumers are MFMA operands writes fp16, halving its store and the consumer's load. */
-int astts_op_gemm_ex(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
-                     const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
-                     int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                     int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope,
-                     astts_stream_t stream);
-/* astts_op_gemm_ex for RAGGED batches (one vocoder pass over utterances of different lengths: HiFTGenerator.inference behind
- * /root/reference/tts_with_rag.py:195, which the reference runs one utterance at a time): input time steps at or beyond
- * in_lens[batch row] (int32 [m / t_out]) are read as zero -- each row convolves as a sequence of its own length with the
+ *               * row_scale[m] + residual[m, n],      m = b*t_out + t, zero outside [0, t_in).
+ * x_f16 / out_f16 != 0: fp16 activation input and / or output (lda / ldc then count halfs).  A producer whose only consumers are
+ * MFMA operands writes fp16, halving its store and the consumer's load.
+ * in_lens (int32 [m / t_out], or NULL), for RAGGED batches (one vocoder pass over utterances of different lengths:
+ * HiFTGenerator.inference behind /root/reference/tts_with_rag.py:195, which the reference runs one utterance at a time): input
+ * time steps at or beyond in_lens[batch row] are read as zero -- each row convolves as a sequence of its own length with the
  * convolution's zero padding behind it.  Output rows beyond a row's own length hold unspecified values. */
-int astts_op_gemm_lens(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
-                       const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
-                       int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                       int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
-                       astts_stream_t stream);
+int astts_op_gemm(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
+                  const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
+                  int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
+                  int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
+                  astts_stream_t stream);
 /* Latency-sized GEMM for batches of a few hundred rows (the wide decode engine: one nn.Linear of TransformerLM's decoder layers for
  * every row of a 33 .. 256-row decode batch, /root/reference/tts_with_rag.py:195 -> cosyvoice llm.inference, one launch per
  * projection): out[m, n] = act(x[m, :] . w[n, :] + bias[n]) + residual[m, n].  x fp32 or fp16 [m, lda], w fp16 [>= n rows, k]
@@ -192,11 +175,17 @@ int astts_op_gemm_rows(const void* x, int32_t x_f16, const void* w_f16, const fl
 /* Decode-sized GEMM (m <= 32, weight-bandwidth bound) with the fusions that take whole launches out of
  * an LM decode step: optional row gather (x row of output row i = x[gather[i]], i.e. an embedding lookup),
  * optional LayerNorm(gamma, beta, eps) over the cin inputs of every row applied while loading, and an
- * optional second destination for the output columns >= n_split (out2[m*ldc2 + n - n_split], fp32 or fp16). */
+ * optional second destination for the output columns >= n_split (out2[m*ldc2 + n - n_split], fp32 or fp16).
+ * workspace (or NULL) enables split-K for deep, narrow shapes (K >= 2048 onto <= 2048 columns, no gather / LayerNorm: the FFN-out
+ * projection of a decode step): 4 K slices per column block, the last slice to arrive adds the partial sums in slice order, so
+ * results are reproducible.  The workspace (astts_op_gemm_fused_workspace_bytes(), 256-byte aligned) must be ZERO on first use
+ * and is left zeroed where it matters; launches sharing it must be ordered on one stream. */
+size_t astts_op_gemm_fused_workspace_bytes(void);
 int astts_op_gemm_fused(const float* x, const int32_t* gather, const float* ln_gamma, const float* ln_beta, float ln_eps,
                         const void* w_f16, const float* bias, const float* residual, float* out, void* out2, int32_t out2_f16,
                         int32_t m, int32_t n, int32_t n_split, int32_t cin, int32_t cin_pad, int32_t lda, int32_t ldc,
-                        int32_t ldc2, int32_t ldr, int32_t act, float alpha, float slope, astts_stream_t stream);
+                        int32_t ldc2, int32_t ldr, int32_t act, float alpha, float slope, void* workspace, size_t workspace_bytes,
+                        astts_stream_t stream);
 /* Row-complete GEMM with the residual add and the NEXT LayerNorm fused into the epilogue (flow-decoder transformer blocks:
  * attention-out and FFN-out projections, n == 256 == one workgroup's column range):
  *   out[m, :] = x[m, :] @ w^T + bias + residual[m, :]      (fp32, the new residual stream)
@@ -206,13 +195,16 @@ int astts_op_gemm_fused(const float* x, const int32_t* gather, const float* ln_g
  * LayerNorm launch -- a 32-row x 256-column workgroup streams the whole weight (0.25-0.5 MB) and only 172 of them exist, so the
  * flow engine keeps the two launches; the operator stays available for wider row counts.
  * (diffusers BasicTransformerBlock: `hidden = attn(norm1(hidden)) + hidden; hidden = ff(norm3(hidden)) + hidden`, [EXT]). */
+int astts_op_gemm_ln(const void* x_f16, const void* w_f16, const float* bias, const float* residual, float* out,
+                     const float* ln_gamma, const float* ln_beta, float ln_eps, void* ln_out_f16, int64_t m, int32_t n, int32_t cin,
+                     int32_t cin_pad, int32_t lda, int32_t ldc, int32_t ldr, int32_t ld_ln, astts_stream_t stream);
 /* Tile choice of the LDS-DMA ring GEMM (fp16 activations): -1 = by shape (default; env ASTTS_GEMM_RING overrides), 0 = ring
  * kernel off (register-staged tiles), 1 = 128x128 two-stage, 2 = 128x64 two-stage, 3 = 64x64 four-stage, 4 = 256x256 two-stage
  * with eight waves on one barrier per K tile, 5 = the same tile on the eight-phase schedule (what "by shape" picks for large GEMMs: the
  * embedder's projections, the kNN scan of >= 64 queries; results bit-identical to 4).  Process-global
  * test / tuning switch: the parity tests run the benchmark's projection shapes through every tile. */
 int astts_op_gemm_set_ring_mode(int32_t mode);
-/* Which kernel astts_op_gemm / _ex / _lens runs for a shape: a pure host query (no stream, no GPU call) of the rule the launcher itself
+/* Which kernel astts_op_gemm runs for a shape: a pure host query (no stream, no GPU call) of the rule the launcher itself
  * switches on, so that a test can assert the tile it means to exercise.  plain != 0: taps == 1, stride == 1, pad == 0, t_in == t_out and
  * no in_lens; x_aligned != 0: fp16 x at a 16-byte aligned address with lda % 8 == 0 (what the ring kernels' LDS-DMA staging needs; not
  * looked at otherwise).  Honours astts_op_gemm_set_ring_mode / ASTTS_GEMM_RING (0: never RING).  -> ASTTS_GEMM_KIND_* or ASTTS_ERR_INVALID.
@@ -229,35 +221,16 @@ int astts_op_gemm_set_ring_mode(int32_t mode);
 #define ASTTS_GEMM_KIND_T64K64 6
 int astts_op_gemm_kernel_kind(int64_t m, int32_t n, int32_t cin, int32_t cin_pad, int32_t taps, int32_t plain, int32_t x_f16,
                               int32_t out_f16, int32_t x_aligned);
-int astts_op_gemm_ln(const void* x_f16, const void* w_f16, const float* bias, const float* residual, float* out,
-                     const float* ln_gamma, const float* ln_beta, float ln_eps, void* ln_out_f16, int64_t m, int32_t n, int32_t cin,
-                     int32_t cin_pad, int32_t lda, int32_t ldc, int32_t ldr, int32_t ld_ln, astts_stream_t stream);
-/* Same, with a workspace that enables split-K for deep, narrow shapes (K >= 2048 onto <= 2048 columns, no gather / LayerNorm:
- * the FFN-out projection of a decode step): 4 K slices per column block, the last slice to arrive adds the partial sums in
- * slice order, so results are reproducible.  The workspace (astts_op_gemm_fused_workspace_bytes(), 256-byte aligned) must
- * be ZERO on first use and is left zeroed where it matters; launches sharing it must be ordered on one stream. */
-size_t astts_op_gemm_fused_workspace_bytes(void);
-int astts_op_gemm_fused_ws(const float* x, const int32_t* gather, const float* ln_gamma, const float* ln_beta, float ln_eps,
-                        const void* w_f16, const float* bias, const float* residual, float* out, void* out2, int32_t out2_f16,
-                        int32_t m, int32_t n, int32_t n_split, int32_t cin, int32_t cin_pad, int32_t lda, int32_t ldc,
-                        int32_t ldc2, int32_t ldr, int32_t act, float alpha, float slope, void* workspace, size_t workspace_bytes,
-                           astts_stream_t stream);
-int astts_op_layernorm(const float* x, const float* gamma, const float* beta, float* y, int64_t rows, int32_t c,
-                       int32_t ldx, int32_t ldy, float eps, astts_stream_t stream);
-/* _ex forms: out_f16 != 0 writes fp16 (ldy in halfs) for outputs whose only consumers are MFMA operands. */
-int astts_op_layernorm_ex(const float* x, const float* gamma, const float* beta, void* y, int32_t out_f16, int64_t rows,
-                          int32_t c, int32_t ldx, int32_t ldy, float eps, astts_stream_t stream);
-/* relu_scale > 0: y = relu_scale * max(LayerNorm(x), 0) -- the LM input embedding's LayerNorm -> ReLU -> * sqrt(d) in one launch. */
-int astts_op_layernorm_relu(const float* x, const float* gamma, const float* beta, void* y, int32_t out_f16, int64_t rows,
-                            int32_t c, int32_t ldx, int32_t ldy, float eps, float relu_scale, astts_stream_t stream);
-int astts_op_groupnorm_ex(const float* x, const int32_t* lens, const float* gamma, const float* beta,
-                          const float* add_bc, void* y, int32_t out_f16, int32_t b, int32_t t, int32_t c, int32_t groups,
-                          float eps, int32_t act_mish, void* workspace, size_t workspace_bytes, astts_stream_t stream);
+/* out_f16 != 0 (here and in astts_op_groupnorm) writes fp16 (ldy in halfs) for outputs whose only consumers are MFMA operands.
+ * relu_scale > 0: y = relu_scale * max(LayerNorm(x), 0) -- the LM input embedding's LayerNorm -> ReLU -> * sqrt(d) in one launch;
+ * relu_scale == 0: the plain LayerNorm. */
+int astts_op_layernorm(const float* x, const float* gamma, const float* beta, void* y, int32_t out_f16, int64_t rows,
+                       int32_t c, int32_t ldx, int32_t ldy, float eps, float relu_scale, astts_stream_t stream);
 size_t astts_op_groupnorm_workspace_bytes(int32_t b, int32_t t, int32_t groups);
 /* y = act(GroupNorm(x over the first lens[b] rows)) (+ add_bc[b, c]); rows >= lens[b] are written as 0. */
 int astts_op_groupnorm(const float* x, const int32_t* lens, const float* gamma, const float* beta,
-                       const float* add_bc, float* y, int32_t b, int32_t t, int32_t c, int32_t groups, float eps,
-                       int32_t act_mish, void* workspace, size_t workspace_bytes, astts_stream_t stream);
+                       const float* add_bc, void* y, int32_t out_f16, int32_t b, int32_t t, int32_t c, int32_t groups,
+                       float eps, int32_t act_mish, void* workspace, size_t workspace_bytes, astts_stream_t stream);
 #define ASTTS_EL_SNAKE 0
 #define ASTTS_EL_LEAKY 1
 #define ASTTS_EL_ADD 2
@@ -275,48 +248,37 @@ int astts_op_elementwise(int32_t op, const float* x, const float* z, const float
                          int64_t total, int32_t t, int32_t c, float s, float s2, astts_stream_t stream);
 int astts_op_embedding(const float* table, const int32_t* ids, float* y, int64_t rows, int32_t c, int32_t ldy,
                        int32_t vocab, float scale, astts_stream_t stream);
+/* in_lens / out_lens (ragged batches): row b is resampled from in_lens[b] to out_lens[b] steps (rows padded to t_in / t_out);
+ * NULL = uniform. */
 int astts_op_interp_linear(const float* x, float* y, int32_t b, int32_t t_in, int32_t t_out, int32_t c,
-                           astts_stream_t stream);
-/* ragged form: row b is resampled from in_lens[b] to out_lens[b] steps (rows padded to t_in / t_out); NULL = uniform. */
-int astts_op_interp_linear_ex(const float* x, float* y, int32_t b, int32_t t_in, int32_t t_out, int32_t c,
-                              const int32_t* in_lens, const int32_t* out_lens, astts_stream_t stream);
+                           const int32_t* in_lens, const int32_t* out_lens, astts_stream_t stream);
 int astts_op_time_embedding(const float* t, float* y, int32_t b, int32_t dim, float scale, astts_stream_t stream);
 /* espnet relative-position attention, head dim 64; tq == 1 selects the KV-cache decode kernel.
- * ld* = time-step strides, *_bs = batch strides (elements): batch-major and time-major layouts both work. */
-int astts_op_attn_relpos(const float* q, const float* k, const float* v, const float* pos, const float* bias_u,
-                         const float* bias_v, const int32_t* lens, float* out, int32_t b, int32_t h, int32_t tq,
-                         int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp, int64_t q_bs, int64_t k_bs,
-                         int64_t o_bs, int32_t q_pos0, int32_t pos_center, int32_t causal, float scale,
-                         astts_stream_t stream);
-/* _ex: K/V (e.g. a KV cache) and/or the position table may be fp16 (ldk / k_bs / ldp then count halfs).
+ * ld* = time-step strides, *_bs = batch strides (elements): batch-major and time-major layouts both work.
+ * kv_f16 / pos_f16 != 0: K/V (e.g. a KV cache) and/or the position table are fp16 (ldk / k_bs / ldp then count halfs).
  * key_start[b] (or NULL): first valid key of row b -- rows of a ragged batch are LEFT-padded to a common length
  * (relative positions make that exact) and keys < key_start[b] are masked. */
-int astts_op_attn_relpos_ex(const float* q, const void* k, const void* v, int32_t kv_f16, const void* pos, int32_t pos_f16,
-                            const float* bias_u, const float* bias_v, const int32_t* lens, const int32_t* key_start, float* out,
-                            int32_t b, int32_t h, int32_t tq, int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp,
-                            int64_t q_bs, int64_t k_bs, int64_t o_bs, int32_t q_pos0, int32_t pos_center, int32_t causal,
-                            float scale, astts_stream_t stream);
-/* masked multi-head attention (flash-style MFMA), head dim 64. */
-int astts_op_attn_mha(const float* q, const float* k, const float* v, const int32_t* lens, float* out, int32_t b,
-                      int32_t h, int32_t t, int32_t ldq, int32_t ldk, int32_t ldo, float scale, astts_stream_t stream);
-int astts_op_attn_mha_ex(const void* q, const void* k, const void* v, int32_t in_f16, const int32_t* lens, void* out,
-                         int32_t out_f16, int32_t b, int32_t h, int32_t t, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
-                         astts_stream_t stream);
+int astts_op_attn_relpos(const float* q, const void* k, const void* v, int32_t kv_f16, const void* pos, int32_t pos_f16,
+                         const float* bias_u, const float* bias_v, const int32_t* lens, const int32_t* key_start, float* out,
+                         int32_t b, int32_t h, int32_t tq, int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp,
+                         int64_t q_bs, int64_t k_bs, int64_t o_bs, int32_t q_pos0, int32_t pos_center, int32_t causal,
+                         float scale, astts_stream_t stream);
+/* masked multi-head attention (flash-style MFMA), head dim 64; q / k / v fp16 when in_f16 != 0, out fp16 when out_f16 != 0. */
+int astts_op_attn_mha(const void* q, const void* k, const void* v, int32_t in_f16, const int32_t* lens, void* out,
+                      int32_t out_f16, int32_t b, int32_t h, int32_t t, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
+                      astts_stream_t stream);
 size_t astts_op_nsf_source_workspace_bytes(int32_t b, int32_t tm);
 int astts_op_nsf_source(const float* f0, const float* phase0, const float* noise, const float* lin_w, const float* lin_b,
                         float* out, int32_t b, int32_t tm, int32_t upsample, int32_t n_harm_plus1, float sample_rate,
                         float sine_amp, float noise_std, float voiced_threshold, void* workspace, size_t workspace_bytes,
                         astts_stream_t stream);
-int astts_op_stft16(const float* x, float* y, int32_t b, int64_t n_samples, astts_stream_t stream);
 /* ragged batches: lens int32 [b] = samples of each row (a multiple of 4, >= 16; NULL: n_samples).  A row is transformed as a signal of
  * its own length (the reflection at its end mirrors its own last samples); frames behind lens[b] / 4 are zero. */
-int astts_op_stft16_lens(const float* x, float* y, int32_t b, int64_t n_samples, const int32_t* lens, astts_stream_t stream);
-int astts_op_istft16(const float* y, float* wav, int32_t b, int64_t frames, float mag_clip, float audio_limit,
-                     astts_stream_t stream);
+int astts_op_stft16(const float* x, float* y, int32_t b, int64_t n_samples, const int32_t* lens, astts_stream_t stream);
 /* ragged batches: frame_lens int32 [b] = frames of each row (NULL: frames); a row's overlap-add sees its own frames only, samples behind
  * 4 (frame_lens[b] - 1) are zero. */
-int astts_op_istft16_lens(const float* y, float* wav, int32_t b, int64_t frames, float mag_clip, float audio_limit, const int32_t* frame_lens,
-                          astts_stream_t stream);
+int astts_op_istft16(const float* y, float* wav, int32_t b, int64_t frames, float mag_clip, float audio_limit, const int32_t* frame_lens,
+                     astts_stream_t stream);
 /* Frontend signal processing on the GPU (the reference does both on the host inside CosyVoice's frontend
  * [EXT], reached from load_wav / inference_* at tts_with_rag.py:180-195):
  * polyphase resampler  y[f * up + p] = sum_j kern[p][j] * x[f * down + j - width]  (kern [up][2 width + down]: the Hann-windowed
@@ -343,12 +305,12 @@ int astts_op_kaldi_fbank(const float* wav, const float* window, const float* mel
                          int32_t hop, int32_t n_fft, int32_t n_mels, float scale, float preemph, float log_floor, astts_stream_t stream);
 /* The learned half of the frontend: glue operators of the CAM++ speaker network (campplus.onnx [EXT]) and the
  * speech tokenizer (speech_tokenizer_v1.onnx [EXT]) that CosyVoice(model_dir) loads (tts_with_rag.py:159) and runs on every prompt
- * (tts_with_rag.py:179-195); their contractions run on astts_op_gemm_* / astts_op_attn_mha_ex, the quantiser's arg-min on
+ * (tts_with_rag.py:179-195); their contractions run on astts_op_gemm_* / astts_op_attn_mha, the quantiser's arg-min on
  * astts_knn_* with ASTTS_METRIC_L2 (csrc/ops_frontend.hip; host: astts/frontend_nets.py; definition: oracle/frontend_nets.py).
  * affine_act: y[r, k] = act(x[r, k] * scale[k] + shift[k]) (eval-mode BatchNorm + ReLU in front of a convolution; scale / shift NULL
  *   = identity; act 0 none, 1 relu; x / y fp32 or fp16 with row strides ldx / ldy).
  * freq_unfold: y[b, fo, t, kf * c + k] = x[b, fo * sf + kf - (nkf - 1) / 2, t, k] (0 outside the input rows) as fp16: the nkf = 3
- *   frequency rows of a 3 x 3 convolution window side by side, so that the convolution is a 3-tap astts_op_gemm_ex over time.
+ *   frequency rows of a 3 x 3 convolution window side by side, so that the convolution is a 3-tap astts_op_gemm over time.
  * ftc_to_tfc: [b, f, t, c] -> [b, t, f * c].
  * cam_context: ctx[b, s, k] = mean_t h[b, t, k] + mean over segment s (seg_len frames, the last one shorter) of h[b, t, k].
  * cam_gate: out[b, t, k] = y[b, t, k] * sigmoid(m[b, t / seg_len, k]) with output row stride ldo (a column block of the dense
@@ -434,18 +396,15 @@ size_t astts_lm_workspace_bytes(const astts_lm_t* h, int32_t b);
  * key_start int32 [b] or NULL (left-padded ragged prefixes); tokens_out int32 [b, n_steps]; logits_out [b, n_steps, vocab_out] or NULL.  The EOS logit is masked for the
  * first eos_min_steps steps (pass n_steps for fixed-length decoding), or per row for eos_min_rows[b] steps when that
  * device array is given (ragged batches); rows keep decoding after an EOS -- the caller
- * truncates at the first EOS id (== speech_vocab). */
+ * truncates at the first EOS id (== speech_vocab).
+ * The call issues steps [s_begin, s_end) of the n_steps decode: (0, n_steps) is the whole decode; shorter ranges are stream=True of
+ * /root/reference/tts_for_dialog.py:188, vc_from_dir.py:18 (upstream's LM thread hands tokens to token2wav hop by hop).  The ranges
+ * of one decode are issued in order on ONE stream with the same kv_cache, tokens_out (the sampler's history) and workspace (it
+ * carries the logits from one range to the next). */
 int astts_lm_decode(astts_lm_t* h, const float* logits0, void* const* kv_cache, const int32_t* key_start, int32_t t_max,
-                    int32_t b, int32_t pos0, int32_t n_steps, const float* uniforms, const int32_t* forced_tokens, int32_t eos_min_steps,
-                    const int32_t* eos_min_rows, int32_t* tokens_out, float* logits_out, void* workspace, size_t workspace_bytes,
-                    astts_stream_t stream);
-/* Steps [s_begin, s_end) of that n_steps decode (stream=True of /root/reference/tts_for_dialog.py:188, vc_from_dir.py:18: upstream's
- * LM thread hands tokens to token2wav hop by hop).  The ranges of one decode are issued in order on ONE stream with the same
- * kv_cache, tokens_out (the sampler's history) and workspace (it carries the logits from one range to the next). */
-int astts_lm_decode_range(astts_lm_t* h, const float* logits0, void* const* kv_cache, const int32_t* key_start, int32_t t_max,
-                          int32_t b, int32_t pos0, int32_t n_steps, int32_t s_begin, int32_t s_end, const float* uniforms,
-                          const int32_t* forced_tokens, int32_t eos_min_steps, const int32_t* eos_min_rows, int32_t* tokens_out,
-                          float* logits_out, void* workspace, size_t workspace_bytes, astts_stream_t stream);
+                    int32_t b, int32_t pos0, int32_t n_steps, int32_t s_begin, int32_t s_end, const float* uniforms,
+                    const int32_t* forced_tokens, int32_t eos_min_steps, const int32_t* eos_min_rows, int32_t* tokens_out,
+                    float* logits_out, void* workspace, size_t workspace_bytes, astts_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Query-embedder operators: what a Llama-3.2 decoder block needs besides the GEMM family.
@@ -531,16 +490,14 @@ int astts_op_i8_gemm(const int8_t* ca, const float* sca, const int8_t* cb, const
  * [b, t, heads*64].  wqkv_frag: the q | k | v weight [3*heads*64, c] re-ordered by astts_op_tfm_pack_frag (from the row-major
  * astts_op_pack_weight image) into MFMA fragment order; bias fp32 [3*heads*64] or NULL, lens int32 [b] or NULL.  Serves
  * c == 256, t <= 384 (astts_op_tfm_attn_fused_supported); otherwise ASTTS_ERR_UNSUPPORTED and the caller runs
- * astts_op_layernorm_ex + astts_op_gemm_ex + astts_op_attn_mha_ex on the row-major weight. */
+ * astts_op_layernorm + astts_op_gemm + astts_op_attn_mha on the row-major weight.
+ * pf_ptrs / pf_bytes (HOST arrays of n_pf <= 3 entries; n_pf == 0: none): an L2 prefetch of up to three ranges (the NEXT launch's
+ * weights -- every block has its own, cold in L2), touched one 128-byte line per thread while the attention phase runs. */
 int astts_op_tfm_pack_frag(const void* w_f16, void* out_f16, int32_t rows, int32_t k, astts_stream_t stream);
 int astts_op_tfm_attn_fused_supported(int32_t c, int32_t heads, int32_t t);
 int astts_op_tfm_attn_fused(const float* x, const void* wqkv_frag_f16, const float* bias, const int32_t* lens, void* out_f16, int32_t b,
-                            int32_t heads, int32_t t, int32_t c, float eps, float scale, astts_stream_t stream);
-/* Same, plus an L2 prefetch of up to three ranges (the NEXT launch's weights -- every block has its own, cold in L2): touched one
- * 128-byte line per thread while the attention phase runs. */
-int astts_op_tfm_attn_fused_pf(const float* x, const void* wqkv_frag_f16, const float* bias, const int32_t* lens, void* out_f16, int32_t b,
-                               int32_t heads, int32_t t, int32_t c, float eps, float scale, const void* const* pf_ptrs,
-                               const uint32_t* pf_bytes, int32_t n_pf, astts_stream_t stream);
+                            int32_t heads, int32_t t, int32_t c, float eps, float scale, const void* const* pf_ptrs,
+                            const uint32_t* pf_bytes, int32_t n_pf, astts_stream_t stream);
 
 /* The feed-forward half of the same block in one launch: out = x' + W2 gelu(W1 LayerNorm(x') + b1) + b2, x / out fp32 [m, c]
  * (out may alias x).  LayerNorm scale / shift folded into w1 / b1 by the caller; the weights in fragment order
@@ -548,16 +505,12 @@ int astts_op_tfm_attn_fused_pf(const float* x, const void* wqkv_frag_f16, const 
  * attn_f16 == NULL: x' = x.  Otherwise the attention's output projection and residual run as a prologue of the same launch:
  * x' = x + attn Wo^T + bo with attn fp16 [m, k0] (k0 = 256 or 512), wo_frag the [c, k0] weight in fragment order, bo fp32 [c] or
  * NULL; x' is never written to memory.  Serves c == 256, hidden a multiple of 256 up to 4096
- * (astts_op_tfm_ffn_fused_supported); otherwise ASTTS_ERR_UNSUPPORTED and the caller runs astts_op_layernorm_ex +
- * astts_op_gemm_ex. */
+ * (astts_op_tfm_ffn_fused_supported); otherwise ASTTS_ERR_UNSUPPORTED and the caller runs astts_op_layernorm +
+ * astts_op_gemm.  pf_ptr / pf_bytes (NULL / 0: none): an L2 prefetch of one range (the next launch's weights). */
 int astts_op_tfm_ffn_fused_supported(int32_t c, int32_t hidden);
 int astts_op_tfm_ffn_fused(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
                            int64_t m, int32_t c, int32_t hidden, float eps, const void* attn_f16, const void* wo_frag_f16,
-                           const float* bo, int32_t k0, astts_stream_t stream);
-/* Same, plus an L2 prefetch of one range (the next launch's weights). */
-int astts_op_tfm_ffn_fused_pf(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
-                              int64_t m, int32_t c, int32_t hidden, float eps, const void* attn_f16, const void* wo_frag_f16,
-                              const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream);
+                           const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream);
 
 /* ---- HiFT resblock convolution, LDS-staged (csrc/ops_conv_lds.hip): y = conv1d_same(snake_alpha(x)) + bias + res on
  * channels-last [b, l, c] activations, c -> c channels (128 or 256), odd taps, dilation dil, zero padding dil*(taps-1)/2 on
@@ -565,17 +518,14 @@ int astts_op_tfm_ffn_fused_pf(const float* x, const void* w1_frag_f16, const flo
  * w_frag: the Conv1d weight re-ordered by astts_op_conv_pack_frag from the astts_op_pack_weight image [c, taps, c]; bias /
  * res (fp32 [b, l, c]) optional.  Outputs, either or both: y (fp32 or fp16) and acc (fp32): acc = (acc_add ? acc : 0) +
  * acc_scale * y -- the mean over the parallel resblocks.  Outputs may not alias x (workgroups read halo rows of their
- * neighbours); res may alias y.  astts_op_conv1d_snake_supported tells whether a shape is served. */
+ * neighbours); res may alias y.  astts_op_conv1d_snake_supported tells whether a shape is served.
+ * RAGGED batches: lens int32 [b] = frames of each sequence (NULL: l).  Frames at or beyond a sequence's length are read as zero (it
+ * convolves as if alone, zero padding behind it) and are not written; tiles wholly behind the end are skipped. */
 int astts_op_conv_pack_frag(const void* w_f16, void* out_f16, int32_t rows, int32_t taps, int32_t k, astts_stream_t stream);
 int astts_op_conv1d_snake_supported(int32_t c, int32_t taps, int32_t dil);
 int astts_op_conv1d_snake(const void* x, int32_t x_f16, const float* alpha, const void* w_frag_f16, const float* bias, const float* res,
                           void* y, int32_t y_f16, float* acc, float acc_scale, int32_t acc_add, int32_t b, int32_t l, int32_t c,
-                          int32_t taps, int32_t dil, astts_stream_t stream);
-/* the same over a RAGGED batch: lens int32 [b] = frames of each sequence (NULL: l).  Frames at or beyond a sequence's length are read as
- * zero (it convolves as if alone, zero padding behind it) and are not written; tiles wholly behind the end are skipped. */
-int astts_op_conv1d_snake_lens(const void* x, int32_t x_f16, const float* alpha, const void* w_frag_f16, const float* bias, const float* res,
-                               void* y, int32_t y_f16, float* acc, float acc_scale, int32_t acc_add, int32_t b, int32_t l, int32_t c,
-                               int32_t taps, int32_t dil, const int32_t* lens, astts_stream_t stream);
+                          int32_t taps, int32_t dil, const int32_t* lens, astts_stream_t stream);
 
 /* ---- ResnetBlock1D convolutions with the GroupNorm + Mish passes folded in (csrc/ops_resnet_conv.hip): out = conv1d_same(x') +
  * bias [+ res'] on channels-last fp32 x [b, t, cin] -> out [b, t, 256], 1 or 3 taps, cin = 256 or 512 (the staging transform: 256 only).
@@ -584,18 +534,14 @@ int astts_op_conv1d_snake_lens(const void* x, int32_t x_f16, const float* alpha,
  *   out_stats (optional): (count, mean, M2) of THIS convolution's output per (sequence, 32-frame tile, group) over the valid frames
  *   -- what a later call takes as in_stats / res_stats (astts_op_resnet_conv_stats_floats(b, t) floats).
  * mask = (frame < lens[b]); lens NULL = all frames.  A ResNet block is three calls: conv 1 (out_stats), conv 2 (in_stats = those,
- * out_stats), 1x1 conv (res = conv 2's output, res_stats).  w_frag: astts_op_conv_pack_frag image. */
+ * out_stats), 1x1 conv (res = conv 2's output, res_stats).  w_frag: astts_op_conv_pack_frag image.
+ * pf_ptr / pf_bytes (NULL / 0: none): an L2 prefetch of one range (the next launch's weights). */
 size_t astts_op_resnet_conv_stats_floats(int32_t b, int32_t t);
 int astts_op_resnet_conv_supported(int32_t cin, int32_t cout, int32_t groups, int32_t taps);
 int astts_op_resnet_conv(const float* x, const void* w_frag_f16, const float* bias, float* out, const float* in_stats, const float* in_gamma,
                          const float* in_beta, const float* in_add, const float* res, const float* res_stats, const float* res_gamma,
                          const float* res_beta, float* out_stats, const int32_t* lens, int32_t b, int32_t t, int32_t cin, int32_t taps,
-                         float eps, astts_stream_t stream);
-/* Same, plus an L2 prefetch of one range (the next launch's weights). */
-int astts_op_resnet_conv_pf(const float* x, const void* w_frag_f16, const float* bias, float* out, const float* in_stats, const float* in_gamma,
-                            const float* in_beta, const float* in_add, const float* res, const float* res_stats, const float* res_gamma,
-                            const float* res_beta, float* out_stats, const int32_t* lens, int32_t b, int32_t t, int32_t cin, int32_t taps,
-                            float eps, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream);
+                         float eps, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream);
 
 /* ---- flow-matching solver engine: the reference's hot loop #3: ConditionalCFM.solve_euler
  * -> ConditionalDecoder.forward (cosyvoice/flow/flow_matching.py + decoder.py [EXT], behind

@@ -20,8 +20,8 @@ int main() {
             const int iters = 200;
             CK(hipEventRecord(e0, st));
             for (int i = 0; i < iters; ++i) {
-                int rc = astts_op_gemm_ex(x, 1, w, bias, s.res ? res : nullptr, nullptr, out, s.out16, s.m, s.n, s.k, s.k, 1, s.k, s.n, s.res ? s.n : 0,
-                                          s.m, s.m, 1, 1, 0, 0, 1.0f, 0.1f, st);
+                int rc = astts_op_gemm(x, 1, w, bias, s.res ? res : nullptr, nullptr, out, s.out16, s.m, s.n, s.k, s.k, 1, s.k, s.n, s.res ? s.n : 0,
+                                       s.m, s.m, 1, 1, 0, 0, 1.0f, 0.1f, nullptr, st);
                 if (rc) { printf("error %s\n", astts_last_error_string()); return 1; }
             }
             CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));

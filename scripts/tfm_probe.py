@@ -11,11 +11,11 @@ L = _lib.load()
 wfrag = ops.tfm_pack_frag(pw)
 for sc, what in ((0.125, 'whole kernel'),):
     for _ in range(50):
-        _lib.check(L.astts_op_tfm_attn_fused(x.data_ptr(), wfrag.data_ptr(), pw.bias.data_ptr(), None, out.data_ptr(), b, heads, t, c, 1e-5, sc, _lib.stream_ptr()))
+        _lib.check(L.astts_op_tfm_attn_fused(x.data_ptr(), wfrag.data_ptr(), pw.bias.data_ptr(), None, out.data_ptr(), b, heads, t, c, 1e-5, sc, None, None, 0, _lib.stream_ptr()))
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(300):
-        L.astts_op_tfm_attn_fused(x.data_ptr(), wfrag.data_ptr(), pw.bias.data_ptr(), None, out.data_ptr(), b, heads, t, c, 1e-5, sc, _lib.stream_ptr())
+        L.astts_op_tfm_attn_fused(x.data_ptr(), wfrag.data_ptr(), pw.bias.data_ptr(), None, out.data_ptr(), b, heads, t, c, 1e-5, sc, None, None, 0, _lib.stream_ptr())
     e1.record(); torch.cuda.synchronize()
     print(f'{what}: {e0.elapsed_time(e1) * 1e3 / 300:.2f} us per launch (incl. boundary)')

@@ -1,5 +1,6 @@
 """CPU tests: the C-ABI library loads and exports every symbol include/astts.h declares (no compute
-calls without a GPU), and the host-side logic (Milvus-Lite reader, MilvusClient shim surface)."""
+calls without a GPU), the ctypes signatures and struct mirrors agree with that header, and the host-side
+logic (Milvus-Lite reader, MilvusClient shim surface)."""
 import ctypes
 import json
 import os
@@ -22,6 +23,14 @@ def _header_symbols():
     return sorted(syms)
 
 
+# ABI 6 folded these forms into the base name, which took the general form's signature: base name -> suffixes that are gone
+FOLDED_IN_ABI_6 = {"astts_knn_search": ("_f64", "_masked"), "astts_op_gemm": ("_ex", "_lens"), "astts_op_gemm_fused": ("_ws",),
+                   "astts_op_layernorm": ("_ex", "_relu"), "astts_op_groupnorm": ("_ex",), "astts_op_interp_linear": ("_ex",),
+                   "astts_op_attn_relpos": ("_ex",), "astts_op_attn_mha": ("_ex",), "astts_op_stft16": ("_lens",),
+                   "astts_op_istft16": ("_lens",), "astts_op_conv1d_snake": ("_lens",), "astts_op_tfm_attn_fused": ("_pf",),
+                   "astts_op_tfm_ffn_fused": ("_pf",), "astts_op_resnet_conv": ("_pf",), "astts_lm_decode": ("_range",)}
+
+
 def test_library_exports_every_declared_symbol():
     from astts import _lib
 
@@ -31,12 +40,92 @@ def test_library_exports_every_declared_symbol():
     assert "astts_knn_search" in syms and len(syms) >= 8
     missing = [s for s in syms if not hasattr(lib, s)]
     assert not missing, f"declared in include/*.h but not exported: {missing}"
-    # the ctypes table mirrors the header one to one
-    import astts.frontend_nets  # noqa: F401
-    import astts.ops  # noqa: F401  (register their parts of the ABI)
+    # the ctypes signatures are parsed from the header: no prototype may escape the parser
     assert set(_lib.declared_symbols()) == set(syms)
+    assert len(syms) == 88
+    removed = [base + suffix for base, suffixes in FOLDED_IN_ABI_6.items() for suffix in suffixes]
+    assert len(removed) == 18 and set(FOLDED_IN_ABI_6) <= set(syms)
+    for name in removed:
+        assert name not in syms and not hasattr(lib, name), name
     lib2 = _lib.load()
-    assert lib2.astts_abi_version() == 5
+    assert lib2.astts_abi_version() == 6
+
+
+def test_prototype_parser_on_literals():
+    from ctypes import c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint32, c_void_p
+
+    from astts._lib import parse_prototypes
+
+    text = """
+    /* a comment with a call in it: astts_not_a_prototype(int32_t x); */
+    #define ASTTS_SOMETHING 3
+    typedef void* astts_stream_t;
+    typedef struct { int32_t d, heads; const float *g_w, *g_b; } astts_cfg_t;
+    int astts_abi_version(void);
+    const char* astts_last_error_string(void);
+    size_t astts_ws_bytes(const astts_cfg_t* h, int64_t rows, int32_t k);
+    int astts_read(int32_t kind, double* ms_sum,
+                   int64_t* launches,
+                   float scale, astts_stream_t stream);
+    int astts_prefetch(const void* const* pf_ptrs, const uint32_t* pf_bytes, uint32_t n_pf, float eps, double tol);
+    """
+    assert parse_prototypes(text) == {
+        "astts_abi_version": (c_int32, []),
+        "astts_last_error_string": (c_char_p, []),
+        "astts_ws_bytes": (c_size_t, [c_void_p, c_int64, c_int32]),
+        "astts_read": (c_int32, [c_int32, c_void_p, c_void_p, c_float, c_void_p]),
+        "astts_prefetch": (c_int32, [c_void_p, c_void_p, c_uint32, c_float, c_double]),
+    }
+
+
+@pytest.mark.parametrize("proto", ["int astts_f(unsigned x);", "int astts_f(int32_t a, long b);", "bool astts_f(void);",
+                                   "int astts_f(astts_cfg_t by_value);"])
+def test_prototype_parser_has_no_silent_defaults(proto):
+    from astts._lib import parse_prototypes
+
+    with pytest.raises(ValueError, match="astts_f"):
+        parse_prototypes(proto)
+
+
+def _header_structs():
+    """typedef name -> [(field, kind)] of every ``typedef struct { ... } name;`` of the header; kind is "pointer", "int32_t", "float"
+    or the name of a nested struct."""
+    text = open(os.path.join(ROOT, "include", "astts.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;", text):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *rest = decl.split(",")
+            *type_words, first_name = first.replace("*", " * ").split()
+            base = [w for w in type_words if w not in ("const", "*")]
+            assert len(base) == 1, decl
+            for item in [("*" if "*" in type_words else "") + first_name] + rest:
+                item = item.replace(" ", "")
+                fields.append((item.lstrip("*"), "pointer" if item.startswith("*") else base[0]))
+        out[name] = fields
+    return out
+
+
+def test_ctypes_structs_mirror_the_header():
+    from astts import ops
+
+    mirrors = {"astts_lm_config_t": ops.LmConfig, "astts_lm_globals_t": ops.LmGlobals, "astts_lm_layer_t": ops.LmLayer,
+               "astts_weight_t": ops.Weight, "astts_flow_resnet_t": ops.FlowResnet, "astts_flow_tfm_t": ops.FlowTfm,
+               "astts_flow_block_t": ops.FlowBlock, "astts_flow_config_t": ops.FlowConfig}
+    structs = _header_structs()
+    assert set(structs) == set(mirrors)            # every struct of the header has a mirror, and the other way round
+    in_ops = {v for v in vars(ops).values() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v is not ctypes.Structure}
+    assert in_ops == set(mirrors.values())
+    by_class = {cls: name for name, cls in mirrors.items()}
+
+    def kind(t):
+        if t is ctypes.c_void_p or issubclass(t, ctypes._Pointer):
+            return "pointer"
+        return {ctypes.c_int32: "int32_t", ctypes.c_float: "float"}.get(t) or by_class[t]
+
+    for name, cls in mirrors.items():
+        assert [(f, kind(t)) for f, t in cls._fields_] == structs[name], name
 
 
 def test_product_path_fails_loudly_without_gpu():

@@ -275,7 +275,7 @@ def _stream_inputs():
 
 
 def test_stream_true_live_decode_yields_the_chunks_of_the_one_pass_form(cosy):
-    """stream=True with the LM decoding hop by hop on its own stream while the chunks render (astts_lm_decode_range, _LmTokenStream)
+    """stream=True with the LM decoding hop by hop on its own stream while the chunks render (astts_lm_decode, _LmTokenStream)
     yields BIT-IDENTICAL chunks to decoding the whole segment first and chunking afterwards (rounds 3-4): same prefix, same uniforms,
     same sampler history across the ranges, same render draws -- fixed-length segments (3 chunks) and EOS-terminated ones."""
     import warnings

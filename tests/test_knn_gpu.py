@@ -310,7 +310,7 @@ def test_milvus_client_search_end_to_end(golden_dir, kats):
 
 def test_bank_sharded_shards_on_one_gpu_equal_unsharded():
     """SURVEY.md 8e stress mode, emulated on one GPU: the bank cut into 3 row shards (three StyleBank handles), every shard
-    searched with all queries (fp64 scores through astts_knn_search_f64), candidates merged by astts.parallel.merge_topk ->
+    searched with all queries (fp64 scores through astts_knn_search's out_score64), candidates merged by astts.parallel.merge_topk ->
     identical to the unsharded search and to the oracle, duplicate rows across shards resolved by the lower row."""
     from astts.knn import StyleBank
     from astts.parallel import merge_topk, shard_bounds

@@ -77,7 +77,7 @@ def test_operator_is_declared_exported_and_registered():
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "astts_op_sample_topk_topp")
     assert "astts_op_sample_topk_topp" in _lib.declared_symbols()
     assert callable(ops.sample_topk_topp)
-    assert _lib.load().astts_abi_version() == 5
+    assert _lib.load().astts_abi_version() == 6
 
 
 def test_operator_refuses_bad_arguments_before_any_launch():

@@ -330,7 +330,7 @@ def test_wide_engine_logits_match_oracle(size, b):
     """Batches of 33 .. 256 rows on the engine's WIDE path (csrc/lm_engine.hip decode_wide: one plain GEMM per projection for all rows --
     the ring kernel on the fp16 LayerNorm output / FFN hidden -- K|V straight into the cache row, per-row decode attention): teacher-forced
     logits of every step within the usual 3e-3 of the oracle (rows sampled for the oracle: it runs one row in ~a second at full size),
-    free-running tokens valid, ragged rows (key_start) included, and steps issued in two ranges == one range (astts_lm_decode_range)."""
+    free-running tokens valid, ragged rows (key_start) included, and steps issued in two ranges == one range (astts_lm_decode)."""
     from astts.synth.config import SynthConfig
     from astts.synth.model import AcousticLM
     from astts.synth.weights import make_all, make_lm_weights

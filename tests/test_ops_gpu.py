@@ -684,9 +684,9 @@ def test_new_entry_points_validate_arguments():
         audio.mel_spectrogram(torch.zeros(1, 100, device=DEV), n_fft=1024, hop=256, win=1024)
     rc = lib.astts_stream_spin(-5, _lib.stream_ptr())
     assert rc == _lib.ERR_INVALID
-    rc = lib.astts_op_gemm_fused_ws(x.data_ptr(), None, None, None, ctypes.c_float(0.0), pw.data.data_ptr(), None, None, out.data_ptr(), None, 0,
-                                    8, 128, 0, 128, 128, 128, 128, 0, 0, 0, ctypes.c_float(1.0), ctypes.c_float(0.1), ctypes.c_void_p(256), 16,
-                                    _lib.stream_ptr())
+    rc = lib.astts_op_gemm_fused(x.data_ptr(), None, None, None, ctypes.c_float(0.0), pw.data.data_ptr(), None, None, out.data_ptr(), None, 0,
+                                 8, 128, 0, 128, 128, 128, 128, 0, 0, 0, ctypes.c_float(1.0), ctypes.c_float(0.1), ctypes.c_void_p(256), 16,
+                                 _lib.stream_ptr())
     assert rc == _lib.ERR_WORKSPACE
     # astts_op_gemm_rows: K must be whole 64-element lines, the split output needs a second destination wide enough, operands aligned
     x16 = torch.randn(64, 128, device=DEV).half()
