@@ -1,0 +1,183 @@
+"""python -m astts.cli.ft_llm -- the reference's src/ft_llm.py: LoRA fine-tuning of the emotion-recognition LLM on the prepared
+``{data_name}.{split}.{k}shot_w{w}_{type}.jsonl`` files, then (``--do_eval_dev`` / ``--do_eval_test``) its weighted-F1 evaluation.
+
+Flags and defaults are the reference's (src/ft_llm.py:163-184), plus this project's ``--allow_random_init`` and ``--base_model_path``.
+Training is astts.llm.train.LoraTrainer: LoRA r = ``--lora_r``, alpha 128 on all seven projections, AdamW, max_grad_norm 0.3,
+constant learning rate with 3 % warm-up, batch 4 x gradient accumulation 4, every row = the chat-formatted conversation including
+the assistant's answer, loss on all of its tokens (SFTTrainer's default).  What the reference does and this does not (NF4 base, bf16,
+packing, LoRA dropout, NEFTune, gradient checkpointing, embedding resize, checkpoint resume, multi-GPU, Qwen): DESIGN.md section 2.
+
+Writes ``{output_folder}/{ft_model_id}``: the peft adapter directory (adapter_config.json, adapter_model.safetensors) and
+``train_log.jsonl`` (one line per optimizer step: step, loss, grad_norm, lr, loss_scale, skipped)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import random
+import sys
+
+from astts.cli import evaluate_erc
+
+BATCH, ACCUM, LORA_ALPHA = 4, 4, 128.0
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="LoRA fine-tuning of the ERC LLM (src/ft_llm.py)")
+    p.add_argument("--do_train", action="store_true", default=False, help="fine tuning a LLM model with LoRA")
+    p.add_argument("--do_eval_test", action="store_true", default=False, help="eval on test set")
+    p.add_argument("--do_eval_dev", action="store_true", default=False, help="eval on dev set")
+    p.add_argument("--ft_model_path", type=str, default=None, help="fine-tuned adapter directory (evaluation without training)")
+    p.add_argument("--ft_model_id", type=str, default=None, help="name of the adapter directory under --output_folder")
+    p.add_argument("--prompting_type", type=str, default="spdescV2")
+    p.add_argument("--base_model_id", type=str, default="meta-llama/Llama-2-7b-hf", help="base checkpoint directory (local only)")
+    p.add_argument("--base_model_path", type=str, default=None, help="base checkpoint directory when --base_model_id is a hub name")
+    p.add_argument("--epoch", type=int, default=None)
+    p.add_argument("--max_steps", type=int, default=None)
+    p.add_argument("--lr", type=float, default=2e-4)
+    p.add_argument("--seed", type=int, default=42)
+    p.add_argument("--kshot", type=int, default=0)
+    p.add_argument("--lora_r", type=int, default=32)
+    p.add_argument("--window", type=int, default=5)
+    p.add_argument("--max_seq_len", type=int, default=None)
+    p.add_argument("--data_name", type=str, default="iemocap")
+    p.add_argument("--data_folder", type=str, default="./data/")
+    p.add_argument("--output_folder", type=str, default="./finetuned_llm/")
+    p.add_argument("--allow_random_init", action="store_true", help="train seeded random Llama weights when the base checkpoint does not exist")
+    p.add_argument("--loss_scale", type=float, default=1024.0, help="static power-of-two loss scale of the fp16 backward")
+    p.add_argument("--limit", type=int, default=None, help="use the first N rows of each file only")
+    return p
+
+
+def split_path(args, split: str) -> str:
+    return f"{args.data_folder}/{args.data_name}.{split}.{args.kshot}shot_w{args.window}_{args.prompting_type}.jsonl"
+
+
+def plan_steps(n_rows: int, epoch, max_steps, batch: int = BATCH, accum: int = ACCUM):
+    """-> (optimizer steps, micro-batches per epoch).  ``max_steps`` wins over ``epoch`` when positive, as in TrainingArguments; an
+    epoch's last optimizer step may hold fewer micro-batches."""
+    micro = max(1, -(-n_rows // batch))
+    per_epoch = max(1, -(-micro // accum))
+    if max_steps is not None and max_steps > 0:
+        return int(max_steps), micro
+    return per_epoch * int(epoch if epoch else 3), micro          # TrainingArguments' num_train_epochs default: 3
+
+
+def encode_rows(rows, tokenizer, max_seq_len):
+    """The whole conversation, assistant answer included, chat-formatted (no generation prompt), truncated on the right."""
+    out = []
+    for r in rows:
+        ids = [int(i) for i in tokenizer.encode(evaluate_erc.chatml_prompt(r["messages"], add_generation_prompt=False))]
+        out.append(ids[:max_seq_len] if max_seq_len else ids)
+    return [ids for ids in out if len(ids) >= 2]
+
+
+def collate(seqs):
+    import torch
+    t = max(len(s) for s in seqs)
+    ids = torch.zeros((len(seqs), t), dtype=torch.int64)
+    for i, s in enumerate(seqs):
+        ids[i, :len(s)] = torch.tensor(s)
+    return ids, torch.tensor([len(s) for s in seqs], dtype=torch.int64)
+
+
+def load_base(args):
+    """-> (state dict, shape, tokenizer or None, base directory or None)."""
+    from astts.llm.config import LlamaShape
+    from astts.llm.peft import shape_from_config
+    from astts.llm.weights import load_llama_weights, make_llama_weights
+    base = args.base_model_path or args.base_model_id
+    if base and os.path.isdir(base):
+        tok = None
+        try:
+            from transformers import AutoTokenizer
+            tok = AutoTokenizer.from_pretrained(base)
+        except Exception as e:  # noqa: BLE001
+            print(f"Warning: no tokenizer under '{base}' ({e}); using the hash stand-in")
+        state = load_llama_weights(base)
+        return state, shape_from_config(base, int(state["model.embed_tokens.weight"].shape[0])), tok, base
+    if not (args.allow_random_init or os.environ.get("ASTTS_ALLOW_RANDOM_INIT") == "1"):
+        raise FileNotFoundError(f"no base checkpoint directory at {base!r} (pass --allow_random_init to train seeded random weights)")
+    cfg = LlamaShape.tiny() if os.environ.get("ASTTS_TINY_MODEL") == "1" else LlamaShape.llama32_3b()
+    print(f"Warning: '{base}' not found; seeded RANDOM-INIT Llama weights at {cfg.hidden}-d (explicitly allowed)")
+    return make_llama_weights(cfg, args.seed), cfg, None, None
+
+
+def train(args, state, cfg, tok, base):
+    import torch
+
+    from astts.llm.tokenizer import HashTokenizer
+    from astts.llm.train import LoraTrainer
+    tokenizer = tok or HashTokenizer(cfg)
+    rows = evaluate_erc.read_rows(split_path(args, "train"), args.limit)
+    seqs = encode_rows(rows, tokenizer, args.max_seq_len)
+    if not seqs:
+        raise SystemExit(f"ft_llm: no usable rows in {split_path(args, 'train')}")
+    steps, _ = plan_steps(len(seqs), args.epoch, args.max_steps)
+    out_dir = os.path.join(args.output_folder, args.ft_model_id or "ft_model")
+    os.makedirs(out_dir, exist_ok=True)
+    adapter = None
+    if args.ft_model_path:
+        from astts.llm.peft import load_adapter
+        adapter = load_adapter(args.ft_model_path)
+    trainer = LoraTrainer(state, cfg, r=args.lora_r, lora_alpha=LORA_ALPHA, seed=args.seed, adapter=adapter, lr=args.lr, total_steps=steps,
+                          loss_scale=args.loss_scale, base_model_name_or_path=base or args.base_model_id,
+                          rope_len=max(len(s) for s in seqs) + 64)
+    rng = random.Random(args.seed)
+    order, pos = [], 0
+    with open(os.path.join(out_dir, "train_log.jsonl"), "w") as log:
+        for _ in range(steps):
+            batches = []
+            for _ in range(ACCUM):
+                if pos >= len(order):                       # a new epoch: reshuffle
+                    order, pos = list(range(len(seqs))), 0
+                    rng.shuffle(order)
+                    if batches:
+                        break                               # the epoch's last optimizer step holds what was left
+                batches.append(collate([seqs[i] for i in order[pos:pos + BATCH]]))
+                pos += BATCH
+            rep = trainer.step(batches)
+            rec = {"step": rep.step, "loss": rep.loss, "grad_norm": rep.grad_norm, "lr": rep.lr, "loss_scale": rep.loss_scale, "skipped": rep.skipped}
+            log.write(json.dumps(rec) + "\n")
+            log.flush()
+            print(rec)
+    trainer.save_adapter(out_dir)
+    print(f"adapter saved to {out_dir}")
+    torch.cuda.synchronize()
+    return trainer, out_dir
+
+
+def evaluate(args, split: str, adapter_dir: str, state, cfg, tok, base):
+    """evaluate_erc's evaluation on ``split`` with the adapter: through the adapter directory when there is a base checkpoint
+    directory to load it over, else (random-init runs) on the in-memory base with the adapter read back from the directory."""
+    ev = evaluate_erc.build_parser().parse_args([])
+    ev.data_file, ev.split, ev.seed, ev.limit = split_path(args, split), split, args.seed, args.limit
+    ev.output_folder = args.output_folder
+    if base is not None:
+        ev.model_path, ev.base_model_path = adapter_dir, base
+        return evaluate_erc.main(ev)
+    from astts.llm.embedder import LlamaEmbedder
+    from astts.llm.peft import load_adapter
+    return evaluate_erc.main(ev, embedder=LlamaEmbedder(state, cfg, tokenizer=tok, lora=load_adapter(adapter_dir)))
+
+
+def main(args):
+    if args.prompting_type == "zeroshot":
+        args.kshot = 0
+    print(args)
+    state, cfg, tok, base = load_base(args)
+    adapter_dir = args.ft_model_path or os.path.join(args.output_folder, args.ft_model_id or "ft_model")
+    if args.do_train:
+        _, adapter_dir = train(args, state, cfg, tok, base)
+    results = {}
+    if args.do_eval_test:
+        results["test"] = evaluate(args, "test", adapter_dir, state, cfg, tok, base)
+        print(f"Test result = {results['test'] and results['test'].get('f1_weighted')}")
+    if args.do_eval_dev:
+        results["valid"] = evaluate(args, "valid", adapter_dir, state, cfg, tok, base)
+        print(f"Valid result = {results['valid'] and results['valid'].get('f1_weighted')}")
+    return results
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_known_args(sys.argv[1:])[0])

@@ -1,0 +1,336 @@
+"""LoRA fine-tuning of the Llama decoder on the GPU: what the reference's src/ft_llm.py does with peft + trl + bitsandbytes
+(LoRA r = 32, alpha = 128 on all seven projections, AdamW, max_grad_norm 0.3, constant learning rate with 3 % warm-up), on this
+project's HIP kernels.  DESIGN.md section 2 "Fine-tuning" has the path, the numerics, the memory kept per token and what is not built.
+
+Forward: LlamaDecoder's layer on batch-major right-padded rows, with the LoRA branch unmerged on the frozen fp16 base
+(``y = W x + (scaling B)(A x)``: two more GEMMs per fused projection, A stacked and B block-diagonal over the projections that share
+an input).  Backward: dX of every frozen projection is ``ops.linear`` on the transposed weight packed once at load; attention, the
+norms, SwiGLU, the softmax gradient, the LoRA weight gradients and the optimizer are csrc/train/*.hip (astts.train_ops); RoPE's
+transpose is the RoPE kernel with a negated sine table.  fp16 where a tensor is an MFMA operand, fp32 for the residual stream, its
+gradient, the LoRA masters, their gradients and the Adam moments; a static power-of-two loss scale keeps the fp16 gradients in
+range.  No atomics: a step is bit-for-bit repeatable.
+"""
+from __future__ import annotations
+
+import json
+import math
+import os
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from .config import LlamaShape
+from .peft import PROJ, LoraAdapter
+
+# the fused projections of LlamaDecoder's layer and the peft modules each is made of
+GROUPS = (("wqkv", ("q_proj", "k_proj", "v_proj")), ("wo", ("o_proj",)), ("wgu", ("gate_proj", "up_proj")), ("wd", ("down_proj",)))
+MAX_GRAD_NORM = 0.3
+WARMUP_RATIO = 0.03
+
+
+def proj_shapes(cfg: LlamaShape) -> Dict[str, Tuple[int, int]]:
+    """peft module -> (out features, in features)."""
+    hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
+    return {"q_proj": (hq, cfg.hidden), "k_proj": (hk, cfg.hidden), "v_proj": (hk, cfg.hidden), "o_proj": (cfg.hidden, hq),
+            "gate_proj": (cfg.ffn, cfg.hidden), "up_proj": (cfg.ffn, cfg.hidden), "down_proj": (cfg.hidden, cfg.ffn)}
+
+
+def init_lora(cfg: LlamaShape, r: int, lora_alpha: float, seed: int = 42, base_model_name_or_path: str = "") -> LoraAdapter:
+    """peft's initial adapter: B = 0, A = kaiming_uniform(a = sqrt(5)), i.e. U(-1 / sqrt(in), 1 / sqrt(in)), drawn layer by layer in
+    PROJ's order from ``torch.Generator().manual_seed(seed)`` on the CPU."""
+    g = torch.Generator().manual_seed(seed)
+    ad = LoraAdapter(r=r, lora_alpha=float(lora_alpha), use_rslora=False, targets=tuple(PROJ), base_model_name_or_path=base_model_name_or_path)
+    shapes = proj_shapes(cfg)
+    for i in range(cfg.layers):
+        for p in PROJ:
+            out_f, in_f = shapes[p]
+            bound = 1.0 / math.sqrt(in_f)
+            ad.pairs[(i, p)] = ((torch.rand(r, in_f, generator=g) * 2.0 - 1.0) * bound, torch.zeros(out_f, r))
+    return ad
+
+
+def save_adapter(adapter: LoraAdapter, path: str) -> None:
+    """adapter_config.json + adapter_model.safetensors as peft's save_pretrained writes them (astts.llm.peft.load_adapter reads them)."""
+    from safetensors.torch import save_file
+
+    os.makedirs(path, exist_ok=True)
+    conf = {"peft_type": "LORA", "task_type": "CAUSAL_LM", "base_model_name_or_path": adapter.base_model_name_or_path, "r": adapter.r,
+            "lora_alpha": adapter.lora_alpha, "lora_dropout": 0.0, "bias": "none", "target_modules": list(adapter.targets),
+            "use_rslora": adapter.use_rslora, "use_dora": False, "fan_in_fan_out": False, "modules_to_save": None, "inference_mode": True,
+            "init_lora_weights": True}
+    with open(os.path.join(path, "adapter_config.json"), "w") as f:
+        json.dump(conf, f, indent=2, sort_keys=True)
+    sd = {}
+    for (i, p), (a, b) in sorted(adapter.pairs.items()):
+        sd[f"base_model.model.model.layers.{i}.{PROJ[p]}.lora_A.weight"] = a.detach().to("cpu", torch.float32).contiguous()
+        sd[f"base_model.model.model.layers.{i}.{PROJ[p]}.lora_B.weight"] = b.detach().to("cpu", torch.float32).contiguous()
+    save_file(sd, os.path.join(path, "adapter_model.safetensors"), metadata={"format": "pt"})
+
+
+def warmup_steps(total_steps: int, ratio: float = WARMUP_RATIO) -> int:
+    """transformers' TrainingArguments.get_warmup_steps: ceil(total * ratio)."""
+    return int(math.ceil(total_steps * ratio))
+
+
+def lr_at(step: int, base_lr: float, total_steps: int, ratio: float = WARMUP_RATIO) -> float:
+    """Learning rate of optimizer step ``step`` (0-based), transformers' constant schedule with warm-up:
+    ``base_lr * min(1, step / max(1, warmup))`` -- with a warm-up, the very first step runs at 0, as there."""
+    w = warmup_steps(total_steps, ratio)
+    return base_lr if step >= w else base_lr * step / max(1, w)
+
+
+def next_token_targets(ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+    """ids ``[B, T]`` right-padded, lens ``[B]`` -> int32 ``[B, T]``: the token at position i + 1 while that is a real token, else -1
+    (transformers' shifted labels with the padding ignored)."""
+    b, t = ids.shape
+    nxt = torch.cat([ids[:, 1:], ids.new_zeros(b, 1)], 1)
+    pos = torch.arange(t, device=ids.device)[None, :]
+    return torch.where(pos + 1 < lens.to(ids.device)[:, None].long(), nxt, nxt.new_full((), -1)).to(torch.int32)
+
+
+def clip_multiplier(grad_norm: float, max_norm: float = MAX_GRAD_NORM) -> float:
+    """torch.nn.utils.clip_grad_norm_'s factor: min(1, max_norm / (norm + 1e-6))."""
+    return min(1.0, max_norm / (grad_norm + 1e-6))
+
+
+@dataclass
+class StepReport:
+    step: int
+    loss: float
+    grad_norm: float
+    lr: float
+    loss_scale: float
+    skipped: bool
+
+
+class _Group:
+    """One fused projection's LoRA: masters (views into the trainer's flat buffers) and the packed fp16 operands made from them."""
+    __slots__ = ("name", "parts", "outs", "cin", "a", "ga", "b", "gb", "a_pack", "b_pack", "at_pack", "bt_pack", "bblk")
+
+
+class LoraTrainer:
+    def __init__(self, state: dict, cfg: LlamaShape, device=None, r: int = 32, lora_alpha: float = 128.0, seed: int = 42,
+                 adapter: Optional[LoraAdapter] = None, lr: float = 2e-4, total_steps: int = 1, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, max_grad_norm: float = MAX_GRAD_NORM, warmup_ratio: float = WARMUP_RATIO,
+                 loss_scale: float = 1024.0, head_chunk: int = 1024, base_model_name_or_path: str = "", rope_len: int = 576):
+        from .. import ops, train_ops
+        from .decoder import LlamaDecoder
+
+        assert loss_scale > 0 and math.log2(loss_scale).is_integer(), "the loss scale is a power of two"
+        self.ops, self.tops = ops, train_ops
+        self.cfg = cfg
+        self.dec = LlamaDecoder(state, cfg, device, rope_len=rope_len)
+        self.device = dev = self.dec.device
+        self.adapter0 = adapter if adapter is not None else init_lora(cfg, r, lora_alpha, seed, base_model_name_or_path)
+        self.r, self.lora_alpha, self.scaling = self.adapter0.r, self.adapter0.lora_alpha, self.adapter0.scaling
+        self.base_name = self.adapter0.base_model_name_or_path or base_model_name_or_path
+        self.lr, self.total_steps, self.betas, self.eps, self.weight_decay = lr, total_steps, betas, eps, weight_decay
+        self.max_grad_norm, self.warmup_ratio, self.loss_scale, self.head_chunk = max_grad_norm, warmup_ratio, float(loss_scale), int(head_chunk)
+        self.opt_step = 0           # optimizer steps taken (skipped ones do not count)
+        self.sched_step = 0         # scheduler position: every call of step()
+        shapes = proj_shapes(cfg)
+        rr = self.r
+        n = sum(rr * (shapes[p][0] + shapes[p][1]) for p in PROJ) * cfg.layers
+        with torch.cuda.device(dev):
+            self.params = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.m = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.v = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.G: List[Dict[str, _Group]] = []
+            # the frozen weights transposed, for dX = dY W: packed once
+            self.WT: List[Dict[str, object]] = []
+            off = 0
+            for i in range(cfg.layers):
+                gl, wt = {}, {}
+                for name, parts in GROUPS:
+                    g = _Group()
+                    g.name, g.parts = name, parts
+                    g.outs = [shapes[p][0] for p in parts]
+                    g.cin = shapes[parts[0]][1]
+                    R, nout = rr * len(parts), sum(g.outs)
+                    g.a = self.params[off:off + R * g.cin].view(R, g.cin)
+                    g.ga = self.grads[off:off + R * g.cin].view(R, g.cin)
+                    off += R * g.cin
+                    g.b, g.gb = [], []
+                    for j, p in enumerate(parts):
+                        g.a[j * rr:(j + 1) * rr].copy_(self.adapter0.pairs[(i, p)][0])
+                        g.b.append(self.params[off:off + g.outs[j] * rr].view(g.outs[j], rr))
+                        g.gb.append(self.grads[off:off + g.outs[j] * rr].view(g.outs[j], rr))
+                        g.b[-1].copy_(self.adapter0.pairs[(i, p)][1])
+                        off += g.outs[j] * rr
+                    g.bblk = torch.zeros(nout, R, dtype=torch.float32, device=dev)
+                    g.a_pack = ops.PackedWeight(g.a, None, dev)                       # [R, in]:    t = x A^T
+                    g.b_pack = ops.PackedWeight(g.bblk, None, dev)                    # [out, R]:   y += t (scaling B)^T
+                    g.at_pack = ops.PackedWeight(g.a.t().contiguous(), None, dev)     # [in, R]:    dx += dt A
+                    g.bt_pack = ops.PackedWeight(g.bblk.t().contiguous(), None, dev)  # [R, out]:   dt = dy (scaling B)
+                    gl[name] = g
+                    w = torch.cat([state[f"model.layers.{i}.{PROJ[p]}.weight"] for p in parts], 0)
+                    wt[name] = ops.PackedWeight(w.to(dev).t().contiguous(), None, dev)
+                self.G.append(gl)
+                self.WT.append(wt)
+            assert off == n
+            head = state["model.embed_tokens.weight"] if cfg.tie_embeddings else state["lm_head.weight"]
+            self.headT = ops.PackedWeight(head.to(dev).t().contiguous(), None, dev)
+            self.nsq = torch.zeros(1, dtype=torch.float32, device=dev)
+            self.repack()
+
+    # ------------------------------------------------------------------------------------------------ parameters
+    def _pack_into(self, pw, src: torch.Tensor) -> None:
+        """astts_op_pack_weight of fp32 ``src`` [n, cin] into the existing image of ``pw`` (a device kernel; the padding stays zero)."""
+        from .. import _lib
+        src = src.contiguous()
+        assert src.shape == (pw.n, pw.cin) and src.dtype == torch.float32
+        _lib.check(_lib.load().astts_op_pack_weight(src.data_ptr(), pw.data.data_ptr(), pw.n, 1, pw.cin, pw.n_pad, pw.cin_pad, _lib.stream_ptr()))
+
+    def repack(self) -> None:
+        """The fp16 GEMM operands of every LoRA pair from the fp32 masters: after load and after every optimizer step."""
+        rr = self.r
+        for gl in self.G:
+            for g in gl.values():
+                o = 0
+                for j, b in enumerate(g.b):                      # block-diagonal scaling * B: projection j's rank columns feed its rows only
+                    torch.mul(b, self.scaling, out=g.bblk[o:o + g.outs[j], j * rr:(j + 1) * rr])
+                    o += g.outs[j]
+                self._pack_into(g.a_pack, g.a)
+                self._pack_into(g.b_pack, g.bblk)
+                self._pack_into(g.at_pack, g.a.t())
+                self._pack_into(g.bt_pack, g.bblk.t())
+
+    def adapter(self) -> LoraAdapter:
+        """The current masters as a LoraAdapter (CPU, fp32)."""
+        ad = LoraAdapter(r=self.r, lora_alpha=self.lora_alpha, use_rslora=self.adapter0.use_rslora, targets=tuple(PROJ),
+                         base_model_name_or_path=self.base_name)
+        rr = self.r
+        for i, gl in enumerate(self.G):
+            for g in gl.values():
+                for j, p in enumerate(g.parts):
+                    ad.pairs[(i, p)] = (g.a[j * rr:(j + 1) * rr].detach().cpu().clone(), g.b[j].detach().cpu().clone())
+        return ad
+
+    def named_grads(self) -> Dict[Tuple[int, str, str], torch.Tensor]:
+        """(layer, module, "A" | "B") -> the accumulated gradient (a view; it carries the loss scale)."""
+        out, rr = {}, self.r
+        for i, gl in enumerate(self.G):
+            for g in gl.values():
+                for j, p in enumerate(g.parts):
+                    out[(i, p, "A")] = g.ga[j * rr:(j + 1) * rr]
+                    out[(i, p, "B")] = g.gb[j]
+        return out
+
+    def save_adapter(self, path: str) -> None:
+        save_adapter(self.adapter(), path)
+
+    # ------------------------------------------------------------------------------------------------ forward / backward
+    def _fwd(self, x16: torch.Tensor, w, g: _Group, residual=None, out_dtype=torch.float32):
+        """base GEMM in fp32 (+ residual), then the LoRA branch on top of it -> (y, t = x A^T fp16)."""
+        ops = self.ops
+        base = ops.linear(x16, w, residual=residual)
+        t = ops.linear(x16, g.a_pack, out_dtype=torch.float16)
+        return ops.linear(t, g.b_pack, residual=base, out_dtype=out_dtype), t
+
+    def _bwd(self, dy: torch.Tensor, x16: torch.Tensor, t: torch.Tensor, wt, g: _Group, first: bool, out_dtype=torch.float32) -> torch.Tensor:
+        """dy [rows, out] (fp16, or fp32: rounded where it becomes an operand) -> dx [rows, in]; adds this micro-batch's dA, dB."""
+        ops, tops = self.ops, self.tops
+        dt = ops.linear(dy, g.bt_pack, out_dtype=torch.float16)                     # [rows, R] = dy (scaling B)
+        dx = ops.linear(dt, g.at_pack, residual=ops.linear(dy, wt), out_dtype=out_dtype)
+        tops.lora_grad(dt, x16, out=g.ga, accumulate=not first)                     # dA (all parts at once) = dt^T x
+        o, rr = 0, self.r
+        for j in range(len(g.parts)):                                               # dB_j = scaling dy_j^T t_j
+            tops.lora_grad(dy[:, o:o + g.outs[j]], t[:, j * rr:(j + 1) * rr], out=g.gb[j], alpha=self.scaling, accumulate=not first)
+            o += g.outs[j]
+        return dx
+
+    def forward(self, ids: torch.Tensor, lens: torch.Tensor, keep: bool = False):
+        """ids [B, T] right-padded, lens [B] -> (sum of next-token log-likelihoods over the real targets [1] fp32 on the device, number
+        of targets, saved state for backward when ``keep``)."""
+        ops, cfg, dec = self.ops, self.cfg, self.dec
+        b, t = ids.shape
+        ids = ids.to(self.device)
+        lens32 = lens.to(self.device, torch.int32).contiguous()
+        cos, sin = dec._rope_for(t)
+        hq, hk, eps = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim, cfg.rms_eps
+        rows = b * t
+        x = ops.embedding(dec.embed, ids).view(rows, cfg.hidden)
+        saved = []
+        for L, G in zip(dec.L, self.G):
+            h1 = ops.rmsnorm(x, L["n1"], eps)
+            qkv, t_qkv = self._fwd(h1, L["wqkv"], G["wqkv"], out_dtype=torch.float16)
+            qkv3 = qkv.view(b, t, hq + 2 * hk)
+            ops.rope_llama_(qkv3, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)
+            ao = ops.attn_gqa(qkv3[..., :hq], qkv3[..., hq:hq + hk], qkv3[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens32).view(rows, hq)
+            x1, t_o = self._fwd(ao, L["wo"], G["wo"], residual=x)
+            h2 = ops.rmsnorm(x1, L["n2"], eps)
+            gu, t_gu = self._fwd(h2, L["wgu"], G["wgu"], out_dtype=torch.float16)
+            act = ops.swiglu(gu)
+            x2, t_d = self._fwd(act, L["wd"], G["wd"], residual=x1)
+            if keep:
+                saved.append((x, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d))
+            x = x2
+        hf = ops.rmsnorm(x, dec.norm, eps)
+        targets = next_token_targets(ids, lens32).reshape(rows).contiguous()
+        lp, lse = ops.head_logprob(hf, dec.head, targets, want_lse=True, vocab=cfg.vocab)
+        count = int((lens.clamp(min=1) - 1).sum())
+        return lp.sum(dtype=torch.float32), count, ((saved, x, hf, targets, lse, lens32, b, t) if keep else None)
+
+    def backward(self, kept, denom: int, first: bool) -> None:
+        """Accumulates d(loss_scale / denom * sum of token losses) / d(every A and B) into ``self.grads`` (``first``: overwrites)."""
+        ops, tops, cfg, dec = self.ops, self.tops, self.cfg, self.dec
+        saved, xf, hf, targets, lse, lens32, b, t = kept
+        rows, eps = b * t, cfg.rms_eps
+        hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
+        cos, sin = dec._rope_for(t)
+        nsin = -sin
+        dh = torch.empty((rows, cfg.hidden), dtype=torch.float32, device=self.device)
+        for r0 in range(0, rows, self.head_chunk):                       # the logits plane: head_chunk rows at a time
+            r1 = min(rows, r0 + self.head_chunk)
+            logits = ops.linear(hf[r0:r1], dec.head)
+            tops.xent_grad_(logits, lse[r0:r1], targets[r0:r1], self.loss_scale / denom)
+            ops.gemm(logits, self.headT, out=dh[r0:r1])
+        dx = torch.zeros((rows, cfg.hidden), dtype=torch.float32, device=self.device)
+        tops.rmsnorm_bwd_(dx, dh, xf, dec.norm, eps)
+        for L, G, WT, s in zip(reversed(dec.L), reversed(self.G), reversed(self.WT), reversed(saved)):
+            x0, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d = s
+            dact = self._bwd(dx, act, t_d, WT["wd"], G["wd"], first, out_dtype=torch.float16)
+            dgu = tops.swiglu_bwd(dact, gu)
+            dh2 = self._bwd(dgu, h2, t_gu, WT["wgu"], G["wgu"], first)
+            tops.rmsnorm_bwd_(dx, dh2, x1, L["n2"], eps)
+            dao = self._bwd(dx, ao, t_o, WT["wo"], G["wo"], first, out_dtype=torch.float16)
+            dqkv = tops.attn_gqa_bwd(qkv3, dao.view(b, t, hq), cfg.heads, cfg.kv_heads, cfg.head_dim, lens32)
+            ops.rope_llama_(dqkv, cos, nsin, cfg.heads + cfg.kv_heads, cfg.head_dim)          # the rotation's transpose
+            dh1 = self._bwd(dqkv.view(rows, hq + 2 * hk), h1, t_qkv, WT["wqkv"], G["wqkv"], first)
+            tops.rmsnorm_bwd_(dx, dh1, x0, L["n1"], eps)
+
+    def loss(self, ids: torch.Tensor, lens: torch.Tensor) -> float:
+        """Mean next-token cross-entropy over the real targets at the current parameters (forward only)."""
+        s, count, _ = self.forward(ids, lens)
+        return -float(s) / max(count, 1)
+
+    # ------------------------------------------------------------------------------------------------ optimizer
+    def accumulate(self, batches: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> float:
+        """Forward + backward of the micro-batches of one optimizer step -> the mean loss over ALL their targets (what transformers'
+        Trainer optimises under gradient accumulation: the token count of the whole accumulated batch normalises every micro-batch)."""
+        denom = max(1, sum(int((lens.clamp(min=1) - 1).sum()) for _, lens in batches))
+        total = 0.0
+        for j, (ids, lens) in enumerate(batches):
+            s, _, kept = self.forward(ids, lens, keep=True)
+            self.backward(kept, denom, first=j == 0)
+            total += float(s)
+        return -total / denom
+
+    def step(self, batches: Sequence[Tuple[torch.Tensor, torch.Tensor]]) -> StepReport:
+        """One optimizer step over ``batches`` (gradient accumulation).  A non-finite gradient norm skips the update and halves the scale."""
+        loss = self.accumulate(batches)
+        scale = self.loss_scale
+        self.tops.sumsq(self.grads, out=self.nsq)
+        norm = math.sqrt(float(self.nsq)) / scale if math.isfinite(float(self.nsq)) else float("nan")
+        lr = lr_at(self.sched_step, self.lr, self.total_steps, self.warmup_ratio)
+        self.sched_step += 1
+        if not math.isfinite(norm):
+            self.loss_scale = scale / 2.0
+            return StepReport(self.sched_step, loss, float("nan"), lr, scale, True)
+        self.opt_step += 1
+        self.tops.adamw_(self.params, self.grads, self.m, self.v, self.opt_step, lr, self.betas[0], self.betas[1], self.eps,
+                         self.weight_decay, grad_mul=clip_multiplier(norm, self.max_grad_norm) / scale)
+        self.repack()
+        return StepReport(self.sched_step, loss, norm, lr, scale, False)

@@ -1,0 +1,115 @@
+"""Python wrappers of libastts_train.so: the backward and optimizer kernels of LoRA fine-tuning (csrc/train/*.hip).  Tensors are
+torch CUDA tensors, the launch goes to the current stream, nothing synchronises and nothing falls back to PyTorch."""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+
+from . import _lib, _lib_train
+
+check = _lib_train.check
+
+
+def _L():
+    return _lib_train.load()
+
+
+def _st():
+    return _lib.stream_ptr()
+
+
+def _ws(nbytes: int, device) -> torch.Tensor:
+    return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+
+
+def attn_gqa_bwd(qkv: torch.Tensor, dout: torch.Tensor, heads: int, kv_heads: int, head_dim: int,
+                 lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal GQA attention backward.  ``qkv`` fp16 ``[B, T, (heads + 2 kv_heads) * hd]`` = rotated q | rotated k | v; ``dout`` fp16
+    ``[B, T, heads * hd]``; ``lens`` int32 ``[B]`` (right padding) -> dq | dk | dv fp16, laid out as ``qkv`` (still in the rotated basis)."""
+    assert qkv.is_cuda and qkv.dtype == dout.dtype == torch.float16 and qkv.dim() == dout.dim() == 3
+    assert qkv.is_contiguous() and dout.is_contiguous(), "attn_gqa_bwd takes whole planes"
+    b, t, w = qkv.shape
+    assert w == (heads + 2 * kv_heads) * head_dim and dout.shape == (b, t, heads * head_dim), (qkv.shape, dout.shape)
+    if lens is not None:
+        assert lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (b,) and lens.is_contiguous()
+    out = torch.empty_like(qkv)
+    ws = _ws(_L().astts_train_attn_gqa_bwd_workspace_bytes(b, t, heads), qkv.device)
+    check(_L().astts_train_attn_gqa_bwd(qkv.data_ptr(), dout.data_ptr(), None if lens is None else lens.data_ptr(), out.data_ptr(), b, t,
+                                        heads, kv_heads, head_dim, w, heads * head_dim, w, 1.0 / math.sqrt(head_dim), ws.data_ptr(),
+                                        ws.numel(), _st()))
+    return out
+
+
+def rmsnorm_bwd_(dres: torch.Tensor, dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
+    """``dres += d rmsnorm(x, w) / dx applied to dy``: all fp32, ``[..., c]`` contiguous; the weight is frozen (no dw)."""
+    for t in (dres, dy, x, w):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), (t.dtype, t.shape)
+    c = x.shape[-1]
+    assert dres.shape == dy.shape == x.shape and w.shape == (c,)
+    check(_L().astts_train_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(), dres.data_ptr(), x.numel() // c, c, float(eps), _st()))
+    return dres
+
+
+def swiglu_bwd(dout: torch.Tensor, gate_up: torch.Tensor) -> torch.Tensor:
+    """``dout`` fp16 ``[..., f]``, ``gate_up`` fp16 ``[..., 2f]`` -> d(gate | up) fp16 ``[..., 2f]``."""
+    assert dout.is_cuda and dout.dtype == gate_up.dtype == torch.float16 and dout.is_contiguous() and gate_up.is_contiguous()
+    f = dout.shape[-1]
+    assert gate_up.shape == (*dout.shape[:-1], 2 * f), (dout.shape, gate_up.shape)
+    out = torch.empty_like(gate_up)
+    check(_L().astts_train_swiglu_bwd(dout.data_ptr(), gate_up.data_ptr(), out.data_ptr(), dout.numel() // f, f, _st()))
+    return out
+
+
+def xent_grad_(logits: torch.Tensor, lse: torch.Tensor, targets: torch.Tensor, scale: float) -> torch.Tensor:
+    """In place: fp32 logits ``[rows, vocab]`` -> ``(softmax - onehot(target)) * scale``; rows with target -1 -> zeros."""
+    assert logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1
+    rows, vocab = logits.shape
+    assert lse.dtype == torch.float32 and lse.shape == (rows,) and lse.is_contiguous()
+    assert targets.dtype == torch.int32 and targets.shape == (rows,) and targets.is_contiguous()
+    check(_L().astts_train_xent_grad(logits.data_ptr(), logits.stride(0), lse.data_ptr(), targets.data_ptr(), rows, vocab, float(scale), _st()))
+    return logits
+
+
+def lora_grad_row_split() -> int:
+    return int(_L().astts_train_lora_grad_row_split())
+
+
+def lora_grad(u: torch.Tensor, x: torch.Tensor, out: Optional[torch.Tensor] = None, alpha: float = 1.0,
+              accumulate: bool = False) -> torch.Tensor:
+    """``G[n, k] = (accumulate ? G : 0) + alpha * sum_rows u[row, n] * x[row, k]``: ``u`` ``[rows, n]`` fp16 or fp32 (rounded to fp16),
+    ``x`` ``[rows, k]`` fp16, both possibly column slices of wider planes (unit column stride); ``out`` fp32 ``[n, k]``."""
+    assert u.is_cuda and u.dim() == 2 and x.dim() == 2 and u.shape[0] == x.shape[0] and u.stride(1) == 1 and x.stride(1) == 1
+    assert u.dtype in (torch.float16, torch.float32) and x.dtype == torch.float16, (u.dtype, x.dtype)
+    rows, n = u.shape
+    k = x.shape[1]
+    if out is None:
+        assert not accumulate
+        out = torch.empty((n, k), dtype=torch.float32, device=u.device)
+    assert out.dtype == torch.float32 and out.shape == (n, k) and out.stride(1) == 1
+    ws = _ws(_L().astts_train_lora_grad_workspace_bytes(rows, n, k), u.device)
+    check(_L().astts_train_lora_grad(u.data_ptr(), 1 if u.dtype == torch.float32 else 0, u.stride(0), x.data_ptr(), x.stride(0),
+                                     out.data_ptr(), out.stride(0), rows, n, k, float(alpha), 1 if accumulate else 0, ws.data_ptr(),
+                                     ws.numel(), _st()))
+    return out
+
+
+def sumsq(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sum of squares of a flat fp32 buffer -> fp32 ``[1]`` on the device (not finite exactly when an element is not)."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()
+    if out is None:
+        out = torch.empty((1,), dtype=torch.float32, device=x.device)
+    ws = _ws(_L().astts_train_sumsq_workspace_bytes(x.numel()), x.device)
+    check(_L().astts_train_sumsq(x.data_ptr(), x.numel(), out.data_ptr(), ws.data_ptr(), ws.numel(), _st()))
+    return out
+
+
+def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float, beta1: float = 0.9,
+           beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, grad_mul: float = 1.0) -> None:
+    """One AdamW step (``step`` >= 1) in place on flat fp32 buffers; the gradient counts as ``grad_mul * g``."""
+    for t in (p, g, m, v):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous() and t.numel() == p.numel()
+    assert step >= 1
+    check(_L().astts_train_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1), float(beta2),
+                                 float(eps), float(weight_decay), 1.0 - beta1 ** step, 1.0 - beta2 ** step, float(grad_mul), _st()))
