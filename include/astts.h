@@ -343,9 +343,13 @@ int astts_op_ras_sample_ex(const float* logits, int32_t* history, const float* u
 
 /* ------------------------------------------------------------------------------------------
  * Acoustic-transformer decode engine: the autoregressive loop of TransformerLM.inference (one speech
- * token per step) issued from C++ with no host synchronisation -- 5 launches per layer and step.  Batches of <= 8 rows
- * take the decode-step kernels of csrc/lm_step.hip (73 launches per step), wider ones the operator chain (74);
- * ASTTS_LM_ENGINE=v1|v2 forces one of them.
+ * token per step) issued from C++ with no host synchronisation.  Which step engine a call takes (csrc/lm_engine.hip; launches
+ * per step at the 14 layers of CosyVoice-300M, the sampler included):
+ *   33 .. ASTTS_LM_MAX_ROWS rows: "wide", plain GEMMs over all rows, 7 launches per layer: 103 (117 with ASTTS_LM_WIDE_GEMM=tile);
+ *   <= 32 rows: "v2", the decode-step kernels of csrc/lm_step.hip, 5 launches per layer: 72 (73 without globals.embed_table),
+ *     whenever the cache and the position tables are fp16 (kv_f16, pos_f16), d and ffn are multiples of 64 and d <= 1024;
+ *   <= 32 rows otherwise, or with ASTTS_LM_ENGINE=v1 in the environment (read per call): "v1", the operator chain
+ *     astts_op_gemm_fused / astts_op_attn_relpos, 5 launches per layer: 74.
  * All pointers are device pointers that must outlive the handle (weights packed by
  * astts_op_pack_weight; fp32 biases / norms / tables).
  * ------------------------------------------------------------------------------------------ */
@@ -398,7 +402,7 @@ size_t astts_lm_workspace_bytes(const astts_lm_t* h, int32_t b);
  * device array is given (ragged batches); rows keep decoding after an EOS -- the caller
  * truncates at the first EOS id (== speech_vocab).
  * The call issues steps [s_begin, s_end) of the n_steps decode: (0, n_steps) is the whole decode; shorter ranges are stream=True of
- * /root/reference/tts_for_dialog.py:188, vc_from_dir.py:18 (upstream's LM thread hands tokens to token2wav hop by hop).  The ranges
+ * the reference's tts_for_dialog.py:188 and vc_from_dir.py:18 (upstream's LM thread hands tokens to token2wav hop by hop).  The ranges
  * of one decode are issued in order on ONE stream with the same kv_cache, tokens_out (the sampler's history) and workspace (it
  * carries the logits from one range to the next). */
 int astts_lm_decode(astts_lm_t* h, const float* logits0, void* const* kv_cache, const int32_t* key_start, int32_t t_max,

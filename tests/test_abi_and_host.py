@@ -299,3 +299,35 @@ def test_milvus_client_explicit_schema_variant(tmp_path):
     assert c.pks == [1, 2, 3, 4, 5] and c.metas[2] == {"file_id": "f2", "text": "t2"}
     with pytest.raises(pm.MilvusException):
         pm.CollectionSchema(fields=fields[:2])                             # no vector field
+
+
+def test_lm_workspace_bytes_layout():
+    """astts_lm_workspace_bytes is host arithmetic on the handle's config (no GPU): the narrow layout (<= 32 rows, shared by the v1 and
+    v2 step engines) and the wide one (33 .. ASTTS_LM_MAX_ROWS), every slot rounded up to 256 bytes.  Callers hold workspaces of these
+    sizes and the logits slot hands one range of steps over to the next, so the closed forms are restated here."""
+    from astts import _lib, ops
+
+    lib = _lib.load()
+
+    def up(x):
+        return (x + 255) // 256 * 256
+
+    splitk = int(lib.astts_op_gemm_fused_workspace_bytes())
+    assert int(lib.astts_lm_workspace_bytes(None, 8)) == 0
+    for d, heads, ffn, layers, vocab_out in [(128, 2, 256, 2, 65), (1024, 16, 4096, 14, 4097)]:
+        cfg = ops.LmConfig(d=d, heads=heads, ffn=ffn, layers=layers, vocab_out=vocab_out, speech_vocab=vocab_out - 1)
+        glob = ops.LmGlobals()                   # null pointer fields: create copies the structs, the size query reads cfg only
+        lay = (ops.LmLayer * layers)()
+        h = ctypes.c_void_p()
+        assert lib.astts_lm_create(ctypes.byref(cfg), ctypes.byref(glob), lay, ctypes.byref(h)) == 0 and h.value
+        try:
+            for b in (1, 3, 32, 33, 97, 256):
+                if b <= 32:
+                    want = 4 * up(4 * b * d) + up(4 * b * ffn) + up(4 * b * vocab_out) + 2 * up(4 * b) + up(splitk)
+                else:
+                    want = 3 * up(4 * b * d) + up(2 * b * d) + 2 * up(4 * b * d) + up(2 * b * ffn) + up(4 * b * vocab_out) + up(4 * b)
+                assert int(lib.astts_lm_workspace_bytes(h, b)) == want, (d, b)
+            for b in (0, -1, 257):
+                assert int(lib.astts_lm_workspace_bytes(h, b)) == 0, (d, b)
+        finally:
+            lib.astts_lm_destroy(h)

@@ -327,7 +327,7 @@ def test_group_steps_stop_each_32_row_group_at_its_own_length():
 
 @pytest.mark.parametrize("size,b", [("tiny", 40), ("tiny", 97), ("full", 72)])
 def test_wide_engine_logits_match_oracle(size, b):
-    """Batches of 33 .. 256 rows on the engine's WIDE path (csrc/lm_engine.hip decode_wide: one plain GEMM per projection for all rows --
+    """Batches of 33 .. 256 rows on the engine's WIDE path (csrc/lm_engine.hip step_wide: one plain GEMM per projection for all rows --
     the ring kernel on the fp16 LayerNorm output / FFN hidden -- K|V straight into the cache row, per-row decode attention): teacher-forced
     logits of every step within the usual 3e-3 of the oracle (rows sampled for the oracle: it runs one row in ~a second at full size),
     free-running tokens valid, ragged rows (key_start) included, and steps issued in two ranges == one range (astts_lm_decode)."""
@@ -386,3 +386,25 @@ def test_wide_engine_logits_match_oracle(size, b):
         dsub = float((lsub - logits[:n2]).abs().max())
         print(f"[parity] wide engine {size} b={b}: rows 0..{n2 - 1} as their own wide batch differ by {dsub:.3e}")
         assert dsub == 0.0
+
+
+@pytest.mark.parametrize("engine", ["v1", "v2"])
+def test_ranges_of_steps_equal_one_call(engine):
+    """The step loop shared by the engines (csrc/lm_engine.hip run_steps): a decode issued as the ranges [0, 1), [1, 4), [4, 6) -- one
+    that starts at 0, one that starts from the logits the previous range left in the workspace, one that ends at n_steps and so breaks
+    before its last forward pass -- gives the tokens and logits of ONE call, bit for bit (free-running sampling on the device)."""
+    from astts.synth.config import SynthConfig
+    from astts.synth.weights import make_all
+
+    cfg = SynthConfig.tiny()
+    steps = 6
+    lm, pre, u, _, _ = _setup(cfg, make_all(cfg, 0)["llm"], 3, 7, 11, steps, 321)
+    with _engine(engine):
+        ctx = lm.decode_begin(lm.prefill(pre, steps), u, True, None, return_logits=True)
+        lm.decode_range(ctx, 1)
+        lm.decode_range(ctx, 4)
+        lm.decode_range(ctx)
+        toks, logits = lm.decode_prefilled(lm.prefill(pre, steps), u, True, None, return_logits=True)
+    assert ctx["next"] == steps
+    assert torch.equal(ctx["toks"], toks) and torch.equal(ctx["logits"], logits)
+    assert int(toks.min()) >= 0 and int(toks.max()) < cfg.speech_vocab
