@@ -783,9 +783,11 @@ def rope_llama_ex_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads:
 
 
 def argmax_rows(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """fp32 ``[rows, n]`` -> int32 ``[rows]`` (ties: the lowest index), on the device: the greedy step's token."""
-    x = _f32(x)
-    assert x.dim() == 2 and x.stride(1) == 1
+    """fp32 ``[rows, n]`` (row stride >= n: a column slice of a wider plane is read in place) -> int32 ``[rows]`` (ties: the lowest
+    index), on the device: the greedy step's token."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2, (x.device, x.dtype, x.shape)
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
     if out is None:
         out = torch.empty((x.shape[0],), dtype=torch.int32, device=x.device)
     _lib.check(_L().astts_op_argmax_rows(x.data_ptr(), out.data_ptr(), x.shape[0], x.shape[1], x.stride(0), _st()))
