@@ -814,6 +814,17 @@ int astts_op_attn_relpos(const float* q, const void* k, const void* v, int32_t k
     hipStream_t st = (hipStream_t)stream;
     const int variant = (kv_f16 ? 2 : 0) | (pos_f16 ? 1 : 0);
     if (tq == 1) {
+        // both kernels of this path load q and the biases as float4 and K, V and the position rows four values at a time
+        // (float4 / half4; attn_relpos_rows' half8 loads are gated by al16 below): require what those loads assume
+        const uintptr_t kv_al = kv_f16 ? 7 : 15, pos_al = pos_f16 ? 7 : 15;
+        ASTTS_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)bias_u & 15) == 0 && ((uintptr_t)bias_v & 15) == 0 &&
+                          ((uintptr_t)k & kv_al) == 0 && ((uintptr_t)v & kv_al) == 0 && ((uintptr_t)pos & pos_al) == 0 &&
+                          (ldk & 3) == 0 && (ldp & 3) == 0 && (k_bs & 3) == 0 && (q_bs & 3) == 0,
+                      ASTTS_ERR_INVALID,
+                      "astts_op_attn_relpos: tq == 1 needs 16-byte aligned q / biases, K / V / table aligned to four values, "
+                      "and ldk, ldp, k_bs, q_bs multiples of 4");
+        // neither tq == 1 kernel reads a.causal: a causal query at q_pos0 sees keys 0 .. q_pos0, so bound the keys here
+        a.len_all = (causal && q_pos0 + 1 < tk) ? q_pos0 + 1 : tk;
         a.tk = (tk + 3) & ~3;  // keeps the partial-output area 16-byte aligned (keys are bounded by lens)
         const size_t lds = ((size_t)a.tk + DG * DH) * sizeof(float);
         ASTTS_REQUIRE(lds <= 60 * 1024, ASTTS_ERR_INVALID, "astts_op_attn_relpos: tk=%d too long for the decode kernel", tk);

@@ -257,7 +257,10 @@ int astts_op_time_embedding(const float* t, float* y, int32_t b, int32_t dim, fl
  * ld* = time-step strides, *_bs = batch strides (elements): batch-major and time-major layouts both work.
  * kv_f16 / pos_f16 != 0: K/V (e.g. a KV cache) and/or the position table are fp16 (ldk / k_bs / ldp then count halfs).
  * key_start[b] (or NULL): first valid key of row b -- rows of a ragged batch are LEFT-padded to a common length
- * (relative positions make that exact) and keys < key_start[b] are masked. */
+ * (relative positions make that exact) and keys < key_start[b] are masked.
+ * causal != 0: query i sees keys j <= q_pos0 + i (at tq == 1 the launcher bounds the keys at q_pos0 + 1).
+ * tq == 1 loads four values at a time: q, bias_u, bias_v 16-byte aligned, K / V / pos aligned to four of their elements,
+ * ldk, ldp, k_bs, q_bs multiples of 4 -- ASTTS_ERR_INVALID otherwise. */
 int astts_op_attn_relpos(const float* q, const void* k, const void* v, int32_t kv_f16, const void* pos, int32_t pos_f16,
                          const float* bias_u, const float* bias_v, const int32_t* lens, const int32_t* key_start, float* out,
                          int32_t b, int32_t h, int32_t tq, int32_t tk, int32_t ldq, int32_t ldk, int32_t ldo, int32_t ldp,
