@@ -15,6 +15,34 @@ import torch
 from . import _lib
 
 
+KNN_SCANS = ("DIRECT", "REGISTER", "GEMM", "GEMM_BLOCKS", "GEMM_N_FIRST")      # ASTTS_KNN_SCAN_*
+KNN_FINISHES = ("FUSED", "BLOCKS", "STREAM", "SELECT", "SELECT_MERGE")       # ASTTS_KNN_FINISH_*
+
+
+def _route_groups(n: int, d: int, nq: int, k: int, masked: bool, aligned: bool):
+    lib = _lib.load()
+    rows, scan, finish, passes = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    done = group = 0
+    while done < nq or group == 0:      # (a shape the library refuses raises on group 0)
+        _lib.check(lib.astts_knn_route(n, d, nq, k, 1 if masked else 0, 1 if aligned else 0, group, ctypes.byref(rows), ctypes.byref(scan),
+                                       ctypes.byref(finish), ctypes.byref(passes)))
+        yield rows.value, KNN_SCANS[scan.value], KNN_FINISHES[finish.value], passes.value
+        done += rows.value
+        group += 1
+
+
+def route(n: int, d: int, nq: int, k: int, masked: bool = False, aligned: bool = True):
+    """The launches a search of ``nq`` queries for ``k`` hits against an ``n x d`` bank takes, as the launcher itself decides them
+    (astts_knn_route: a host query, no GPU call): one ``(rows, scan, finish)`` per query group, names from KNN_SCANS / KNN_FINISHES.
+    ``masked``: with a row mask; ``aligned``: the queries at a 16-byte aligned address (every torch allocation is)."""
+    return [g[:3] for g in _route_groups(n, d, nq, k, masked, aligned)]
+
+
+def route_passes(n: int, d: int, nq: int, k: int) -> int:
+    """Selection + re-score passes of that search over one scan per query group: ``ceil(k / 32)`` when ``k > 32``, else 1."""
+    return next(_route_groups(n, d, nq, k, False, True))[3]
+
+
 def _require_gpu() -> None:
     if not torch.cuda.is_available():
         raise RuntimeError("astts.knn needs a ROCm GPU (torch.cuda.is_available() is False); "
@@ -150,6 +178,10 @@ class StyleBank:
             row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
         idx, sc = self.search_device(q.to(self.device), k, force_exact, row_mask=row_mask)
         return idx.cpu().numpy(), sc.cpu().numpy()
+
+    def route(self, nq: int, k: int, masked: bool = False, aligned: bool = True):
+        """``route`` (above) for a search of this bank: ``[(rows, scan, finish), ...]``, one per query group."""
+        return route(self.n, self.d, nq, k, masked, aligned)
 
     def last_fallbacks(self) -> int:
         """How many queries of the last search needed the exact fp64 scan (synchronises)."""

@@ -51,7 +51,9 @@ bool prof_events(int kind, double work, hipEvent_t* e0, hipEvent_t* e1);
 
 // the kNN scan as one GEMM on the LDS-DMA ring kernel (ops_gemm.hip), row panels of one bank tile first
 // (blockmax given: the scores leave scaled -- out = dot * col_scale (+ row_qs * col_bias) -- with the maximum of every (query, 64-row
-// block) beside them; ring kernels only: ASTTS_ERR_INVALID when the shape is outside them)
+// block) beside them; ring kernels only: ASTTS_ERR_INVALID unless gemm_scan_blockmax_ok, which a caller asks BEFORE it plans that scan --
+// the shape and the ring switch in force, astts_op_gemm_set_ring_mode / ASTTS_GEMM_RING, decide it; queries: null = an aligned pointer)
+bool gemm_scan_blockmax_ok(int32_t qg, int64_t n, int32_t dp, const void* queries);
 int gemm_scan(const _Float16* queries, const _Float16* bank, float* out, int32_t qg, int64_t n, int32_t dp, int32_t ldc, hipStream_t st,
               const float* col_scale = nullptr, const float* col_bias = nullptr, const float* row_qs = nullptr, float* blockmax = nullptr,
               int32_t bm_ld = 0);

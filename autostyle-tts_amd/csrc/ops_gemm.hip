@@ -1421,10 +1421,6 @@ static int launch_gemm(const GemmArgs& a, hipStream_t st) {
         ASTTS_CHECK_LAUNCH();
         return ASTTS_OK;
     }
-    if (a.blockmax) {          // (gemm_scan checks the shape; what is left is a ring path switched off: astts_op_gemm_set_ring_mode(0))
-        set_error("gemm_scan: the block-maximum epilogue needs the ring kernels");
-        return ASTTS_ERR_INVALID;
-    }
     switch (kind) {
         case ASTTS_GEMM_KIND_T32: launch_tile<4, 1, 1, 1, 64>(a, st); break;
         case ASTTS_GEMM_KIND_T128: launch_tile<2, 2, 2, 2, 32>(a, st); break;
@@ -1437,6 +1433,15 @@ static int launch_gemm(const GemmArgs& a, hipStream_t st) {
     return ASTTS_OK;
 }
 
+// Will the ring kernels serve the kNN scan of `qg` fp16 query rows [qg][dp] with its block-maximum epilogue?  The kNN route (knn.hip) asks
+// before it plans that scan and gemm_scan checks its arguments with the same answer: gemm_kernel_kind on the GEMM gemm_scan builds, under
+// the ring switch in force.  (n > 64: the maxima are per 64 columns of a wave, i.e. the tiles with TN = 2, and a narrower output gets the
+// 128 x 64 tile.)  queries: null stands for a 16-byte aligned pointer (a host query has none).
+bool gemm_scan_blockmax_ok(int32_t qg, int64_t n, int32_t dp, const void* queries) {
+    return n > 64 && gemm_kernel_kind(qg, (int)n, dp, (int)align_up((size_t)dp, 64), 1, true, true, false, ((uintptr_t)queries & 15) == 0,
+                                      ring_mode_in_force()) == ASTTS_GEMM_KIND_RING;
+}
+
 // the kNN scan as one GEMM (knn.hip): scores[q][n] = <query q, bank row n>, fp16 operands, fp32 out [qg][ldc]; row panels of one bank
 // tile first (GemmArgs::m_first), so that the bank is fetched from HBM once however many 128-query panels there are
 int gemm_scan(const _Float16* queries, const _Float16* bank, float* out, int32_t qg, int64_t n, int32_t dp, int32_t ldc, hipStream_t st,
@@ -1446,9 +1451,10 @@ int gemm_scan(const _Float16* queries, const _Float16* bank, float* out, int32_t
                nullptr, nullptr, nullptr, 0.0f, nullptr, 0, 0, 1, 0, 0};
     a.m_first = 1;
     if (blockmax) {
-        // (only the ring kernels carry that epilogue: their launch conditions, restated -- the caller takes the plain scan otherwise)
-        if (!(qg >= 64 && n > 64 && (dp & 63) == 0 && ((uintptr_t)queries & 15) == 0 && col_scale && (!col_bias || row_qs))) {
-            set_error("gemm_scan: shape outside the ring kernels (qg=%d n=%lld dp=%d)", qg, (long long)n, dp);
+        // (only the ring kernels carry that epilogue -- the caller takes the plain scan otherwise)
+        if (!(gemm_scan_blockmax_ok(qg, n, dp, queries) && col_scale && (!col_bias || row_qs))) {
+            set_error("gemm_scan: the block-maximum epilogue needs the ring kernels (qg=%d n=%lld dp=%d, ring mode %d)", qg, (long long)n, dp,
+                      ring_mode_in_force());
             return ASTTS_ERR_INVALID;
         }
         a.col_scale = col_scale;

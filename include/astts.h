@@ -128,6 +128,25 @@ int astts_knn_last_fallbacks(const astts_knn_t* h, const void* workspace, astts_
 int astts_knn_profile_enable(astts_knn_t* h, int32_t on);
 int astts_knn_profile_read(astts_knn_t* h, double* scan_ms_sum, int64_t* scan_launches);
 
+/* Which launches a search takes: a host query on the shape alone (no GPU, no handle), answered by the plan astts_knn_search itself
+ * runs, under the ASTTS_KNN_* switches of the environment and the ring-kernel switch in force (astts_op_gemm_set_ring_mode /
+ * ASTTS_GEMM_RING).  A search of nq queries against an n x d bank runs in query groups of <= 256 rows, each with ONE scan launch and a
+ * finish; masked: a row mask is given; queries_aligned: the queries sit at a 16-byte aligned address.  For group `group` (0, 1, ...):
+ * its row count, ASTTS_KNN_SCAN_*, ASTTS_KNN_FINISH_* and the selection passes of the search (ceil(k / 32) when k > 32, else 1); null
+ * outputs are skipped.  ASTTS_ERR_INVALID for a group past the last or a shape astts_knn_create / _search would refuse. */
+int astts_knn_route(int64_t n, int32_t d, int32_t nq, int32_t k, int32_t masked, int32_t queries_aligned, int32_t group,
+                    int32_t* rows, int32_t* scan, int32_t* finish, int32_t* passes);
+#define ASTTS_KNN_SCAN_DIRECT 0        /* knn_scan<1,1,DIRECT> on the caller's fp32 queries: no preparation launch */
+#define ASTTS_KNN_SCAN_REGISTER 1      /* knn_scan<QT,RT> (register-streaming, K split on a small bank) behind knn_prep_queries */
+#define ASTTS_KNN_SCAN_GEMM 2          /* one GEMM, bare dot products */
+#define ASTTS_KNN_SCAN_GEMM_BLOCKS 3   /* one GEMM on the ring kernels: scaled scores and the maximum of every (query, 64-row block) */
+#define ASTTS_KNN_SCAN_GEMM_N_FIRST 4  /* the ASTTS_KNN_GEMM_N_FIRST experiment: the GEMM in the projections' tile order */
+#define ASTTS_KNN_FINISH_FUSED 0        /* knn_select_rescore: selection + fp64 re-score of the whole search in one launch */
+#define ASTTS_KNN_FINISH_BLOCKS 1       /* knn_blocks_rescore per group: selection from the block maxima + fp64 re-score */
+#define ASTTS_KNN_FINISH_STREAM 2       /* knn_select_stream per group, then knn_rescore_finalize */
+#define ASTTS_KNN_FINISH_SELECT 3       /* knn_select, one block per query, then knn_rescore_finalize */
+#define ASTTS_KNN_FINISH_SELECT_MERGE 4 /* knn_select per (query, segment) + knn_select_merge, then knn_rescore_finalize */
+
 /* ------------------------------------------------------------------------------------------
  * Synthesis operators.  Replace the tensor arithmetic executed inside the reference's
  * cosyvoice.inference_tts_with_st / inference_zero_shot / inference_vc calls (tts_with_rag.py:195,

@@ -135,20 +135,21 @@ def test_fp32_bank_rows_of_any_norm():
 
 def test_gemm_scan_path_large_query_groups():
     """Query groups of >= 64 against a bank that fills the chip take the scan as one GEMM on the ring kernel: exact and
-    fp16-inexact banks, a tail group below 64 queries, duplicate rows (ties decided by row index), scaled queries."""
+    fp16-inexact banks, a query count that is cut into two equal groups, duplicate rows (ties decided by row index), scaled queries."""
     rng = np.random.default_rng(11)
     bank16 = rng.standard_normal((20000, 256)).astype(np.float16)
     bank16[777] = bank16[123]                       # exact duplicates
     bank16[19999] = bank16[123]
-    q = rng.standard_normal((300, 256)).astype(np.float32)       # groups of 256 + 44 (tail: register-streaming scan)
+    q = rng.standard_normal((300, 256)).astype(np.float32)       # two equal groups of 150, both GEMMs (not 256 + a tail of 44)
     q[5] = bank16[123].astype(np.float32) * 37.5
     q[260] = bank16[777].astype(np.float32) * 1e-3
     sb = _check(bank16, q, 5)
+    assert sb.route(300, 5) == [(150, "GEMM_BLOCKS", "BLOCKS")] * 2 and sb.route(70, 3) == [(70, "GEMM_BLOCKS", "BLOCKS")]
     assert sb.last_fallbacks() <= 75
     _check(bank16, q[:70], 3, force_exact=True, sb=sb)
     bank32 = rng.standard_normal((12000, 384)).astype(np.float32)  # not fp16-representable: the scan plane is a rounded image
     sb32 = _bank(bank32)
-    assert not sb32.scan_plane_exact
+    assert not sb32.scan_plane_exact and sb32.route(130, 3) == [(130, "GEMM_BLOCKS", "BLOCKS")]
     _check(bank32, rng.standard_normal((130, 384)).astype(np.float32), 3, sb=sb32)
 
 
@@ -172,6 +173,8 @@ def test_large_query_group_selection_on_ordered_rows():
     ones = np.ones(n, np.uint8)
     for bank in (asc, asc[::-1].copy()):
         sb = _check(bank, q, 3)
+        for k in (3, 20):
+            assert sb.route(64, k) == [(64, "GEMM_BLOCKS", "BLOCKS")] and sb.route(64, k, masked=True) == [(64, "GEMM", "STREAM")]
         _check(bank, q, 20, sb=sb)
         _check_metric(bank, q, 3, "COSINE", mask=ones, sb=sb)
         _check_metric(bank, q, 20, "COSINE", mask=ones, sb=sb)
@@ -179,6 +182,7 @@ def test_large_query_group_selection_on_ordered_rows():
     ties = few[rng.integers(0, 7, n)]
     qt = rng.standard_normal((70, d)).astype(np.float32)
     sb = _check(ties, qt, 5)
+    assert sb.route(70, 5) == [(70, "GEMM_BLOCKS", "BLOCKS")] and sb.route(70, 5, masked=True) == [(70, "GEMM", "STREAM")]
     _check(ties, few.astype(np.float32).repeat(10, 0), 20, sb=sb)
     _check_metric(ties, qt, 5, "COSINE", mask=ones, sb=sb)
     for metric in ("IP", "L2"):                              # the epilogue's per-row constant (L2) and the plain scale (IP), ties included
@@ -194,9 +198,11 @@ def test_large_query_group_beyond_the_block_maximum_range():
     bank = rng.standard_normal((530000, 64)).astype(np.float16)
     q = bank[rng.integers(0, 530000, 70)].astype(np.float32) + 0.3 * rng.standard_normal((70, 64)).astype(np.float32)
     sb = _check(bank, q, 3)
+    assert sb.route(70, 3) == [(70, "GEMM", "STREAM")] and sb.route(64, 20) == [(64, "GEMM", "STREAM")]
     _check(bank, q[:64], 20, sb=sb)
     small = rng.standard_normal((8200, 128)).astype(np.float16)
-    _check(small, rng.standard_normal((300, 128)).astype(np.float32), 5)
+    sbs = _check(small, rng.standard_normal((300, 128)).astype(np.float32), 5)
+    assert sbs.route(300, 5) == [(150, "GEMM_BLOCKS", "BLOCKS")] * 2
 
 
 def test_duplicates_ties_zero_rows_and_small_banks():
@@ -428,8 +434,11 @@ def test_row_masks(real_bank, metric):
 def test_limits_beyond_32_hits(real_bank, metric):
     """limit up to 1024: 32 certified hits per selection pass over ONE scan, the rows of earlier passes masked out -- the
     concatenation is the oracle's order, through every pass boundary; k > n returns every row, then -1."""
+    from astts.knn import route, route_passes
+
     q = real_bank[:6].astype(np.float32) + 0.25
     sb = _check_metric(real_bank, q, 33, metric)
+    assert sb.route(6, 33) == [(6, "REGISTER", "SELECT")] and route_passes(130, 6144, 6, 33) == 2 and route_passes(130, 6144, 6, 200) == 7
     _check_metric(real_bank, q, 100, metric, sb=sb)
     _check_metric(real_bank, q, 130, metric, sb=sb)
     _check_metric(real_bank, q, 200, metric, sb=sb)                    # more hits than rows
@@ -439,7 +448,10 @@ def test_limits_beyond_32_hits(real_bank, metric):
     rng = np.random.default_rng(8)
     bank = rng.standard_normal((20000, 128)).astype(np.float16)
     qq = rng.standard_normal((300, 128)).astype(np.float32)            # two chunks of <= 256 queries
-    _check_metric(bank, qq, 1024 if metric == "COSINE" else 80, metric, atol=2e-6)
+    kk = 1024 if metric == "COSINE" else 80
+    assert route(20000, 128, 300, kk) == [(256, "GEMM", "STREAM"), (44, "REGISTER", "SELECT_MERGE")]
+    assert route_passes(20000, 128, 300, kk) == (32 if metric == "COSINE" else 3)
+    _check_metric(bank, qq, kk, metric, atol=2e-6)
 
 
 def test_milvus_client_filter_limit_and_metrics(tmp_path):
@@ -480,6 +492,7 @@ def test_small_bank_two_launch_form_at_the_extremes(real_bank, metric):
     image), mixed magnitudes inside one query, a zero query, k larger than the candidate list's fast form."""
     q = real_bank[:12].astype(np.float32)
     sb = _check_metric(real_bank, q * 1e-7, 3, metric)
+    assert sb.route(12, 3) == [(12, "DIRECT", "FUSED")] and sb.route(12, 20) == [(12, "DIRECT", "FUSED")] and sb.route(2, 3) == [(2, "DIRECT", "FUSED")]
     _check_metric(real_bank, q * 1e-3, 3, metric, sb=sb)
     _check_metric(real_bank, q * 3e4, 3, metric, sb=sb)                 # elements up to ~1e5: past 65504
     assert sb.last_fallbacks() == 12
@@ -493,3 +506,53 @@ def test_small_bank_two_launch_form_at_the_extremes(real_bank, metric):
     # a plain run certifies (no query takes the exact scan)
     _check_metric(real_bank, q + 0.3, 3, metric, sb=sb)
     assert sb.last_fallbacks() == 0
+
+
+# ------------------------------------------------------------------------------------------ one search per (scan, finish) route
+ROUTE_CASES = [((64, 128, 5, 3), False, "DIRECT", "FUSED", 1), ((300, 100, 7, 3), False, "REGISTER", "FUSED", 1),
+               ((8193, 64, 9, 3), False, "REGISTER", "SELECT_MERGE", 1), ((4096, 64, 256, 3), False, "GEMM", "FUSED", 1),
+               ((4096, 64, 300, 3), False, "GEMM", "SELECT", 1), ((8200, 128, 128, 5), False, "GEMM_BLOCKS", "BLOCKS", 1),
+               ((8200, 128, 128, 5), True, "GEMM", "STREAM", 1), ((1000, 64, 8, 40), False, "REGISTER", "SELECT", 2),
+               ((8200, 128, 128, 40), False, "GEMM", "STREAM", 2)]
+
+
+def _route_case_data(n, d, nq):
+    rng = np.random.default_rng(n + d + nq)
+    return rng.standard_normal((n, d)).astype(np.float16), rng.standard_normal((nq, d)).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape,masked,scan,finish,passes", ROUTE_CASES,
+                         ids=[f"{c[2]}-{c[3]}-{c[4]}" + ("-masked" if c[1] else "") for c in ROUTE_CASES])
+def test_every_route_matches_oracle(shape, masked, scan, finish, passes):
+    """Every (scan, finish) pair of the plan at the smallest shape that reaches it: the library reports that route
+    for every query group, and the search that takes it returns the oracle's ids and scores.  (SELECT_MERGE behind a GEMM scan exists
+    only under ASTTS_KNN_NO_STREAM_SELECT, a process-start switch.)"""
+    from astts.knn import route_passes
+
+    n, d, nq, k = shape
+    bank, q = _route_case_data(n, d, nq)
+    sb = _bank(bank)
+    groups = sb.route(nq, k, masked=masked)
+    assert sum(g[0] for g in groups) == nq and {g[1:] for g in groups} == {(scan, finish)}, groups
+    assert route_passes(n, d, nq, k) == passes
+    _check_metric(bank, q, k, "COSINE", mask=np.ones(n, np.uint8) if masked else None, sb=sb)
+
+
+def test_block_maximum_route_with_the_ring_kernels_off():
+    """The block-maximum scan runs on the ring kernels only.  With them switched off (astts_op_gemm_set_ring_mode(0), a process-wide GEMM
+    A/B switch) a search in that range takes the plain GEMM scan and the streaming selection, as it does with a row mask, and returns
+    the oracle's result.  (Before the route knew of the switch this search failed with ASTTS_ERR_INVALID: the launcher asked for the
+    block-maximum epilogue whatever the state of the ring kernels.)"""
+    from astts import ops
+
+    n, d, nq, k = 8200, 128, 128, 5
+    bank, q = _route_case_data(n, d, nq)
+    sb = _bank(bank)
+    assert sb.route(nq, k) == [(nq, "GEMM_BLOCKS", "BLOCKS")]
+    ops.set_gemm_ring_mode(0)
+    try:
+        assert sb.route(nq, k) == [(nq, "GEMM", "STREAM")]
+        _check_metric(bank, q, k, "COSINE", sb=sb)
+    finally:
+        ops.set_gemm_ring_mode(-1)
+    assert sb.route(nq, k) == [(nq, "GEMM_BLOCKS", "BLOCKS")]
