@@ -3,9 +3,16 @@
 
 Flags and defaults are the reference's (src/ft_llm.py:163-184), plus this project's ``--allow_random_init`` and ``--base_model_path``.
 Training is astts.llm.train.LoraTrainer: LoRA r = ``--lora_r``, alpha 128 on all seven projections, AdamW, max_grad_norm 0.3,
-constant learning rate with 3 % warm-up, batch 4 x gradient accumulation 4, every row = the chat-formatted conversation including
-the assistant's answer, loss on all of its tokens (SFTTrainer's default).  What the reference does and this does not (NF4 base, bf16,
-packing, LoRA dropout, NEFTune, gradient checkpointing, embedding resize, checkpoint resume, multi-GPU, Qwen): DESIGN.md section 2.
+3 % warm-up, batch 4 x gradient accumulation 4, every row = the chat-formatted conversation including the assistant's answer, loss
+on all of its tokens (SFTTrainer's default).
+
+Four parts of the reference's recipe are flags that default to OFF (the defaults train what this command trained before they
+existed); the reference's own values are ``--lr_scheduler linear`` (scripts/train_llm.sh and train_llm_cn.sh pass it),
+``--lora_dropout 0.05`` (its LoraConfig), ``--neftune_noise_alpha 5`` and ``--packing`` at ``--max_seq_len 1024`` (its SFTTrainer:
+trl's ConstantLengthDataset -- conversations concatenated in file order and cut into chunks of exactly max_seq_len tokens that attend
+across conversation boundaries).  An ``--lr_scheduler`` this command does not know is an error, not a silently constant rate.
+What the reference does and this does not (NF4 base, bf16, gradient checkpointing, embedding resize, checkpoint resume, the
+evaluation every 50 steps with load_best_model_at_end, multi-GPU, Qwen): DESIGN.md section 2.
 
 Writes ``{output_folder}/{ft_model_id}``: the peft adapter directory (adapter_config.json, adapter_model.safetensors) and
 ``train_log.jsonl`` (one line per optimizer step: step, loss, grad_norm, lr, loss_scale, skipped)."""
@@ -46,6 +53,12 @@ def build_parser():
     p.add_argument("--allow_random_init", action="store_true", help="train seeded random Llama weights when the base checkpoint does not exist")
     p.add_argument("--loss_scale", type=float, default=1024.0, help="static power-of-two loss scale of the fp16 backward")
     p.add_argument("--limit", type=int, default=None, help="use the first N rows of each file only")
+    p.add_argument("--lr_scheduler", type=str, default="constant", choices=["constant", "linear"],
+                   help="learning-rate schedule after the 3 %% warm-up (the reference's scripts pass linear)")
+    p.add_argument("--lora_dropout", type=float, default=0.0, help="dropout on the input of every LoRA module (the reference: 0.05)")
+    p.add_argument("--neftune_noise_alpha", type=float, default=0.0, help="NEFTune noise on the embedding output (the reference: 5)")
+    p.add_argument("--packing", action="store_true", default=False,
+                   help="concatenate the conversations and train on chunks of exactly --max_seq_len (default 1024) tokens, as the reference does")
     return p
 
 
@@ -70,6 +83,33 @@ def encode_rows(rows, tokenizer, max_seq_len):
         ids = [int(i) for i in tokenizer.encode(evaluate_erc.chatml_prompt(r["messages"], add_generation_prompt=False))]
         out.append(ids[:max_seq_len] if max_seq_len else ids)
     return [ids for ids in out if len(ids) >= 2]
+
+
+def encode_packed(rows, tokenizer, seq_len: int):
+    """``--packing``: every conversation encoded whole (no truncation), then pack_rows."""
+    texts = [evaluate_erc.chatml_prompt(r["messages"], add_generation_prompt=False) for r in rows]
+    return pack_rows([[int(i) for i in tokenizer.encode(t)] for t in texts], seq_len, [len(t) for t in texts])
+
+
+PACK_SEQ_LEN, PACK_CHARS_PER_TOKEN, PACK_NUM_SEQUENCES = 1024, 3.6, 1024
+
+
+def pack_rows(seqs, seq_len: int, texts_chars):
+    """trl's ConstantLengthDataset (append_concat_token=False, infinite=False): the encoded rows, in file order and with nothing
+    between them, fill buffers of ``seq_len * 3.6 * 1024`` characters of formatted text (``texts_chars[i]`` = the characters of row
+    i; a buffer takes rows until it holds that many); each buffer's tokens are cut into chunks of exactly ``seq_len``, and the
+    buffer's incomplete tail is dropped."""
+    assert len(seqs) == len(texts_chars) and seq_len >= 1
+    max_chars = seq_len * PACK_CHARS_PER_TOKEN * PACK_NUM_SEQUENCES
+    out, i = [], 0
+    while i < len(seqs):
+        tokens, chars = [], 0
+        while i < len(seqs) and chars < max_chars:
+            tokens.extend(seqs[i])
+            chars += texts_chars[i]
+            i += 1
+        out.extend(tokens[o:o + seq_len] for o in range(0, len(tokens) - seq_len + 1, seq_len))
+    return out
 
 
 def collate(seqs):
@@ -110,7 +150,10 @@ def train(args, state, cfg, tok, base):
     from astts.llm.train import LoraTrainer
     tokenizer = tok or HashTokenizer(cfg)
     rows = evaluate_erc.read_rows(split_path(args, "train"), args.limit)
-    seqs = encode_rows(rows, tokenizer, args.max_seq_len)
+    if args.packing:
+        seqs = encode_packed(rows, tokenizer, args.max_seq_len or PACK_SEQ_LEN)
+    else:
+        seqs = encode_rows(rows, tokenizer, args.max_seq_len)
     if not seqs:
         raise SystemExit(f"ft_llm: no usable rows in {split_path(args, 'train')}")
     steps, _ = plan_steps(len(seqs), args.epoch, args.max_steps)
@@ -122,7 +165,8 @@ def train(args, state, cfg, tok, base):
         adapter = load_adapter(args.ft_model_path)
     trainer = LoraTrainer(state, cfg, r=args.lora_r, lora_alpha=LORA_ALPHA, seed=args.seed, adapter=adapter, lr=args.lr, total_steps=steps,
                           loss_scale=args.loss_scale, base_model_name_or_path=base or args.base_model_id,
-                          rope_len=max(len(s) for s in seqs) + 64)
+                          rope_len=max(len(s) for s in seqs) + 64, lora_dropout=args.lora_dropout, neftune_alpha=args.neftune_noise_alpha,
+                          schedule=args.lr_scheduler)
     rng = random.Random(args.seed)
     order, pos = [], 0
     with open(os.path.join(out_dir, "train_log.jsonl"), "w") as log:
@@ -180,4 +224,4 @@ def main(args):
 
 
 if __name__ == "__main__":
-    main(build_parser().parse_known_args(sys.argv[1:])[0])
+    main(build_parser().parse_known_args(sys.argv[1:])[0])        # unknown FLAGS pass, as before; an unknown value of a known flag exits

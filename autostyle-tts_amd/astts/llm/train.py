@@ -1,6 +1,6 @@
 """LoRA fine-tuning of the Llama decoder on the GPU: what the reference's src/ft_llm.py does with peft + trl + bitsandbytes
-(LoRA r = 32, alpha = 128 on all seven projections, AdamW, max_grad_norm 0.3, constant learning rate with 3 % warm-up), on this
-project's HIP kernels.  DESIGN.md section 2 "Fine-tuning" has the path, the numerics, the memory kept per token and what is not built.
+(LoRA r = 32, alpha = 128 on all seven projections, AdamW, max_grad_norm 0.3, constant or linear learning rate with 3 % warm-up, LoRA
+dropout and NEFTune noise from a counter-based generator), on this project's HIP kernels.  DESIGN.md section 2 "Fine-tuning" has the path, the numerics, the memory kept per token and what is not built.
 
 Forward: LlamaDecoder's layer on batch-major right-padded rows, with the LoRA branch unmerged on the frozen fp16 base
 (``y = W x + (scaling B)(A x)``: two more GEMMs per fused projection, A stacked and B block-diagonal over the projections that share
@@ -9,6 +9,12 @@ norms, SwiGLU, the softmax gradient, the LoRA weight gradients and the optimizer
 transpose is the RoPE kernel with a negated sine table.  fp16 where a tensor is an MFMA operand, fp32 for the residual stream, its
 gradient, the LoRA masters, their gradients and the Adam moments; a static power-of-two loss scale keeps the fp16 gradients in
 range.  No atomics: a step is bit-for-bit repeatable.
+
+Regularisers (``lora_dropout``, ``neftune_alpha``; both 0 = the path above, bit for bit).  peft gives every LoRA module its own
+dropout on its input, so q, k and v mask the same ``h1`` independently; the masks are never stored: each is a function of
+(``noise_seed``, layer * 8 + position in PROJ, the forward's ``draw``) that ``lora_down`` regenerates in its operand load,
+``lora_grad_dropout`` (dA) in its operand load and ``lora_dx_dropout`` in its epilogue.  dB needs nothing: ``t`` carries the mask.
+NEFTune adds ``alpha / sqrt(T * hidden) * U(-1, 1)`` to the embedding output of a training forward.
 """
 from __future__ import annotations
 
@@ -50,13 +56,13 @@ def init_lora(cfg: LlamaShape, r: int, lora_alpha: float, seed: int = 42, base_m
     return ad
 
 
-def save_adapter(adapter: LoraAdapter, path: str) -> None:
+def save_adapter(adapter: LoraAdapter, path: str, lora_dropout: float = 0.0) -> None:
     """adapter_config.json + adapter_model.safetensors as peft's save_pretrained writes them (astts.llm.peft.load_adapter reads them)."""
     from safetensors.torch import save_file
 
     os.makedirs(path, exist_ok=True)
     conf = {"peft_type": "LORA", "task_type": "CAUSAL_LM", "base_model_name_or_path": adapter.base_model_name_or_path, "r": adapter.r,
-            "lora_alpha": adapter.lora_alpha, "lora_dropout": 0.0, "bias": "none", "target_modules": list(adapter.targets),
+            "lora_alpha": adapter.lora_alpha, "lora_dropout": float(lora_dropout), "bias": "none", "target_modules": list(adapter.targets),
             "use_rslora": adapter.use_rslora, "use_dora": False, "fan_in_fan_out": False, "modules_to_save": None, "inference_mode": True,
             "init_lora_weights": True}
     with open(os.path.join(path, "adapter_config.json"), "w") as f:
@@ -73,11 +79,21 @@ def warmup_steps(total_steps: int, ratio: float = WARMUP_RATIO) -> int:
     return int(math.ceil(total_steps * ratio))
 
 
-def lr_at(step: int, base_lr: float, total_steps: int, ratio: float = WARMUP_RATIO) -> float:
-    """Learning rate of optimizer step ``step`` (0-based), transformers' constant schedule with warm-up:
-    ``base_lr * min(1, step / max(1, warmup))`` -- with a warm-up, the very first step runs at 0, as there."""
+SCHEDULES = ("constant", "linear")
+
+
+def lr_at(step: int, base_lr: float, total_steps: int, ratio: float = WARMUP_RATIO, schedule: str = "constant") -> float:
+    """Learning rate of optimizer step ``step`` (0-based).  ``"constant"``: transformers' constant schedule with warm-up,
+    ``base_lr * min(1, step / max(1, warmup))`` -- with a warm-up, the very first step runs at 0, as there.  ``"linear"``: its
+    get_linear_schedule_with_warmup, the same warm-up and then ``max(0, (total - step) / max(1, total - warmup))``."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"schedule {schedule!r}: one of {SCHEDULES}")
     w = warmup_steps(total_steps, ratio)
-    return base_lr if step >= w else base_lr * step / max(1, w)
+    if step < w:
+        return base_lr * step / max(1, w)
+    if schedule == "linear":
+        return base_lr * max(0.0, (total_steps - step) / max(1, total_steps - w))
+    return base_lr
 
 
 def next_token_targets(ids: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
@@ -106,18 +122,20 @@ class StepReport:
 
 class _Group:
     """One fused projection's LoRA: masters (views into the trainer's flat buffers) and the packed fp16 operands made from them."""
-    __slots__ = ("name", "parts", "outs", "cin", "a", "ga", "b", "gb", "a_pack", "b_pack", "at_pack", "bt_pack", "bblk")
+    __slots__ = ("name", "parts", "outs", "cin", "a", "ga", "b", "gb", "a_pack", "b_pack", "at_pack", "bt_pack", "bblk", "stream")
 
 
 class LoraTrainer:
     def __init__(self, state: dict, cfg: LlamaShape, device=None, r: int = 32, lora_alpha: float = 128.0, seed: int = 42,
                  adapter: Optional[LoraAdapter] = None, lr: float = 2e-4, total_steps: int = 1, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, max_grad_norm: float = MAX_GRAD_NORM, warmup_ratio: float = WARMUP_RATIO,
-                 loss_scale: float = 1024.0, head_chunk: int = 1024, base_model_name_or_path: str = "", rope_len: int = 576):
+                 loss_scale: float = 1024.0, head_chunk: int = 1024, base_model_name_or_path: str = "", rope_len: int = 576,
+                 lora_dropout: float = 0.0, neftune_alpha: float = 0.0, noise_seed: Optional[int] = None, schedule: str = "constant"):
         from .. import ops, train_ops
         from .decoder import LlamaDecoder
 
         assert loss_scale > 0 and math.log2(loss_scale).is_integer(), "the loss scale is a power of two"
+        assert 0.0 <= lora_dropout < 1.0 and neftune_alpha >= 0.0 and schedule in SCHEDULES, (lora_dropout, neftune_alpha, schedule)
         self.ops, self.tops = ops, train_ops
         self.cfg = cfg
         self.dec = LlamaDecoder(state, cfg, device, rope_len=rope_len)
@@ -127,6 +145,9 @@ class LoraTrainer:
         self.base_name = self.adapter0.base_model_name_or_path or base_model_name_or_path
         self.lr, self.total_steps, self.betas, self.eps, self.weight_decay = lr, total_steps, betas, eps, weight_decay
         self.max_grad_norm, self.warmup_ratio, self.loss_scale, self.head_chunk = max_grad_norm, warmup_ratio, float(loss_scale), int(head_chunk)
+        self.lora_dropout, self.neftune_alpha, self.schedule = float(lora_dropout), float(neftune_alpha), schedule
+        self.noise_seed = int(seed if noise_seed is None else noise_seed)
+        self.draw = 0               # training forwards run so far: the generator's draw of the next one
         self.opt_step = 0           # optimizer steps taken (skipped ones do not count)
         self.sched_step = 0         # scheduler position: every call of step()
         shapes = proj_shapes(cfg)
@@ -148,6 +169,7 @@ class LoraTrainer:
                     g.name, g.parts = name, parts
                     g.outs = [shapes[p][0] for p in parts]
                     g.cin = shapes[parts[0]][1]
+                    g.stream = i * 8 + list(PROJ).index(parts[0])                 # part j draws from stream + j
                     R, nout = rr * len(parts), sum(g.outs)
                     g.a = self.params[off:off + R * g.cin].view(R, g.cin)
                     g.ga = self.grads[off:off + R * g.cin].view(R, g.cin)
@@ -219,31 +241,47 @@ class LoraTrainer:
         return out
 
     def save_adapter(self, path: str) -> None:
-        save_adapter(self.adapter(), path)
+        save_adapter(self.adapter(), path, self.lora_dropout)
 
     # ------------------------------------------------------------------------------------------------ forward / backward
-    def _fwd(self, x16: torch.Tensor, w, g: _Group, residual=None, out_dtype=torch.float32):
-        """base GEMM in fp32 (+ residual), then the LoRA branch on top of it -> (y, t = x A^T fp16)."""
+    def _drop(self, g: _Group, draw: Optional[int]):
+        """The dropout arguments of one fused projection in the forward numbered ``draw`` (None: evaluation, or dropout off)."""
+        if draw is None or self.lora_dropout == 0.0:
+            return None
+        return dict(parts=len(g.parts), r=self.r, p=self.lora_dropout, seed=self.noise_seed, rng_stream=g.stream, draw=draw)
+
+    def _fwd(self, x16: torch.Tensor, w, g: _Group, residual=None, out_dtype=torch.float32, draw: Optional[int] = None):
+        """base GEMM in fp32 (+ residual), then the LoRA branch on top of it -> (y, t = x A^T fp16; under dropout each part of t sees
+        x under its own mask)."""
         ops = self.ops
         base = ops.linear(x16, w, residual=residual)
-        t = ops.linear(x16, g.a_pack, out_dtype=torch.float16)
+        drop = self._drop(g, draw)
+        t = ops.linear(x16, g.a_pack, out_dtype=torch.float16) if drop is None else self.tops.lora_down(x16, g.a_pack, **drop)
         return ops.linear(t, g.b_pack, residual=base, out_dtype=out_dtype), t
 
-    def _bwd(self, dy: torch.Tensor, x16: torch.Tensor, t: torch.Tensor, wt, g: _Group, first: bool, out_dtype=torch.float32) -> torch.Tensor:
-        """dy [rows, out] (fp16, or fp32: rounded where it becomes an operand) -> dx [rows, in]; adds this micro-batch's dA, dB."""
+    def _bwd(self, dy: torch.Tensor, x16: torch.Tensor, t: torch.Tensor, wt, g: _Group, first: bool, out_dtype=torch.float32,
+             draw: Optional[int] = None) -> torch.Tensor:
+        """dy [rows, out] (fp16, or fp32: rounded where it becomes an operand) -> dx [rows, in]; adds this micro-batch's dA, dB.
+        ``draw``: the forward's, whose masks dA and the LoRA part of dx regenerate."""
         ops, tops = self.ops, self.tops
         dt = ops.linear(dy, g.bt_pack, out_dtype=torch.float16)                     # [rows, R] = dy (scaling B)
-        dx = ops.linear(dt, g.at_pack, residual=ops.linear(dy, wt), out_dtype=out_dtype)
-        tops.lora_grad(dt, x16, out=g.ga, accumulate=not first)                     # dA (all parts at once) = dt^T x
+        drop = self._drop(g, draw)
+        if drop is None:
+            dx = ops.linear(dt, g.at_pack, residual=ops.linear(dy, wt), out_dtype=out_dtype)
+            tops.lora_grad(dt, x16, out=g.ga, accumulate=not first)                 # dA (all parts at once) = dt^T x
+        else:
+            dx = tops.lora_dx_dropout(dt, g.at_pack, ops.linear(dy, wt), out_dtype=out_dtype, **drop)
+            tops.lora_grad_dropout(dt, x16, out=g.ga, accumulate=not first, **drop)  # dA_j = dt_j^T (mask_j o x) / (1 - p)
         o, rr = 0, self.r
         for j in range(len(g.parts)):                                               # dB_j = scaling dy_j^T t_j
             tops.lora_grad(dy[:, o:o + g.outs[j]], t[:, j * rr:(j + 1) * rr], out=g.gb[j], alpha=self.scaling, accumulate=not first)
             o += g.outs[j]
         return dx
 
-    def forward(self, ids: torch.Tensor, lens: torch.Tensor, keep: bool = False):
+    def forward(self, ids: torch.Tensor, lens: torch.Tensor, keep: bool = False, train: bool = False):
         """ids [B, T] right-padded, lens [B] -> (sum of next-token log-likelihoods over the real targets [1] fp32 on the device, number
-        of targets, saved state for backward when ``keep``)."""
+        of targets, saved state for backward when ``keep``).  ``train``: dropout and NEFTune act, and the forward takes the next draw
+        of the generator (kept with the state: backward regenerates its masks)."""
         ops, cfg, dec = self.ops, self.cfg, self.dec
         b, t = ids.shape
         ids = ids.to(self.device)
@@ -252,18 +290,23 @@ class LoraTrainer:
         hq, hk, eps = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim, cfg.rms_eps
         rows = b * t
         x = ops.embedding(dec.embed, ids).view(rows, cfg.hidden)
+        draw = None
+        if train:
+            draw, self.draw = self.draw, self.draw + 1
+            if self.neftune_alpha > 0.0:                 # trl's neftune_post_forward_hook: padding positions get noise too
+                self.tops.neftune_(x, self.neftune_alpha / math.sqrt(t * cfg.hidden), self.noise_seed, draw)
         saved = []
         for L, G in zip(dec.L, self.G):
             h1 = ops.rmsnorm(x, L["n1"], eps)
-            qkv, t_qkv = self._fwd(h1, L["wqkv"], G["wqkv"], out_dtype=torch.float16)
+            qkv, t_qkv = self._fwd(h1, L["wqkv"], G["wqkv"], out_dtype=torch.float16, draw=draw)
             qkv3 = qkv.view(b, t, hq + 2 * hk)
             ops.rope_llama_(qkv3, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)
             ao = ops.attn_gqa(qkv3[..., :hq], qkv3[..., hq:hq + hk], qkv3[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens32).view(rows, hq)
-            x1, t_o = self._fwd(ao, L["wo"], G["wo"], residual=x)
+            x1, t_o = self._fwd(ao, L["wo"], G["wo"], residual=x, draw=draw)
             h2 = ops.rmsnorm(x1, L["n2"], eps)
-            gu, t_gu = self._fwd(h2, L["wgu"], G["wgu"], out_dtype=torch.float16)
+            gu, t_gu = self._fwd(h2, L["wgu"], G["wgu"], out_dtype=torch.float16, draw=draw)
             act = ops.swiglu(gu)
-            x2, t_d = self._fwd(act, L["wd"], G["wd"], residual=x1)
+            x2, t_d = self._fwd(act, L["wd"], G["wd"], residual=x1, draw=draw)
             if keep:
                 saved.append((x, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d))
             x = x2
@@ -271,12 +314,12 @@ class LoraTrainer:
         targets = next_token_targets(ids, lens32).reshape(rows).contiguous()
         lp, lse = ops.head_logprob(hf, dec.head, targets, want_lse=True, vocab=cfg.vocab)
         count = int((lens.clamp(min=1) - 1).sum())
-        return lp.sum(dtype=torch.float32), count, ((saved, x, hf, targets, lse, lens32, b, t) if keep else None)
+        return lp.sum(dtype=torch.float32), count, ((saved, x, hf, targets, lse, lens32, b, t, draw) if keep else None)
 
     def backward(self, kept, denom: int, first: bool) -> None:
         """Accumulates d(loss_scale / denom * sum of token losses) / d(every A and B) into ``self.grads`` (``first``: overwrites)."""
         ops, tops, cfg, dec = self.ops, self.tops, self.cfg, self.dec
-        saved, xf, hf, targets, lse, lens32, b, t = kept
+        saved, xf, hf, targets, lse, lens32, b, t, draw = kept
         rows, eps = b * t, cfg.rms_eps
         hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
         cos, sin = dec._rope_for(t)
@@ -291,14 +334,14 @@ class LoraTrainer:
         tops.rmsnorm_bwd_(dx, dh, xf, dec.norm, eps)
         for L, G, WT, s in zip(reversed(dec.L), reversed(self.G), reversed(self.WT), reversed(saved)):
             x0, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d = s
-            dact = self._bwd(dx, act, t_d, WT["wd"], G["wd"], first, out_dtype=torch.float16)
+            dact = self._bwd(dx, act, t_d, WT["wd"], G["wd"], first, out_dtype=torch.float16, draw=draw)
             dgu = tops.swiglu_bwd(dact, gu)
-            dh2 = self._bwd(dgu, h2, t_gu, WT["wgu"], G["wgu"], first)
+            dh2 = self._bwd(dgu, h2, t_gu, WT["wgu"], G["wgu"], first, draw=draw)
             tops.rmsnorm_bwd_(dx, dh2, x1, L["n2"], eps)
-            dao = self._bwd(dx, ao, t_o, WT["wo"], G["wo"], first, out_dtype=torch.float16)
+            dao = self._bwd(dx, ao, t_o, WT["wo"], G["wo"], first, out_dtype=torch.float16, draw=draw)
             dqkv = tops.attn_gqa_bwd(qkv3, dao.view(b, t, hq), cfg.heads, cfg.kv_heads, cfg.head_dim, lens32)
             ops.rope_llama_(dqkv, cos, nsin, cfg.heads + cfg.kv_heads, cfg.head_dim)          # the rotation's transpose
-            dh1 = self._bwd(dqkv.view(rows, hq + 2 * hk), h1, t_qkv, WT["wqkv"], G["wqkv"], first)
+            dh1 = self._bwd(dqkv.view(rows, hq + 2 * hk), h1, t_qkv, WT["wqkv"], G["wqkv"], first, draw=draw)
             tops.rmsnorm_bwd_(dx, dh1, x0, L["n1"], eps)
 
     def loss(self, ids: torch.Tensor, lens: torch.Tensor) -> float:
@@ -313,7 +356,7 @@ class LoraTrainer:
         denom = max(1, sum(int((lens.clamp(min=1) - 1).sum()) for _, lens in batches))
         total = 0.0
         for j, (ids, lens) in enumerate(batches):
-            s, _, kept = self.forward(ids, lens, keep=True)
+            s, _, kept = self.forward(ids, lens, keep=True, train=True)
             self.backward(kept, denom, first=j == 0)
             total += float(s)
         return -total / denom
@@ -324,7 +367,7 @@ class LoraTrainer:
         scale = self.loss_scale
         self.tops.sumsq(self.grads, out=self.nsq)
         norm = math.sqrt(float(self.nsq)) / scale if math.isfinite(float(self.nsq)) else float("nan")
-        lr = lr_at(self.sched_step, self.lr, self.total_steps, self.warmup_ratio)
+        lr = lr_at(self.sched_step, self.lr, self.total_steps, self.warmup_ratio, self.schedule)
         self.sched_step += 1
         if not math.isfinite(norm):
             self.loss_scale = scale / 2.0

@@ -113,3 +113,80 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
     assert step >= 1
     check(_L().astts_train_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(beta1), float(beta2),
                                  float(eps), float(weight_decay), 1.0 - beta1 ** step, 1.0 - beta2 ** step, float(grad_mul), _st()))
+
+
+# ---- the regularisers: LoRA dropout from a counter-based generator (no stored masks) and NEFTune.  The contract of (seed, rng_stream,
+# draw) is in include/train/astts_train.h; part j of a fused projection uses rng_stream + j
+NEFTUNE_STREAM = 0xFFFFFFFF
+
+
+def dropout_threshold(p: float) -> int:
+    """An element is kept iff its 16 random bits are >= this."""
+    return int(math.floor(p * 65536))
+
+
+def dropout_mask(rows: int, cin: int, p: float, seed: int, rng_stream: int, draw: int, device=None) -> torch.Tensor:
+    """The keep mask of one (seed, rng_stream, draw, p): uint8 ``[rows, cin]``.  The training path never stores one; this pins the generator."""
+    out = torch.empty((rows, cin), dtype=torch.uint8, device=device or torch.device("cuda", torch.cuda.current_device()))
+    check(_L().astts_train_dropout_mask(out.data_ptr(), rows, cin, float(p), int(seed), int(rng_stream), int(draw), _st()))
+    return out
+
+
+def neftune_(x: torch.Tensor, mag: float, seed: int, draw: int) -> torch.Tensor:
+    """In place on fp32 ``[..., hidden]``: ``x += mag * (2u - 1)``, u uniform in (0, 1) from the generator's NEFTune stream."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+    hidden = x.shape[-1]
+    check(_L().astts_train_neftune(x.data_ptr(), x.numel() // hidden, hidden, float(mag), int(seed), int(draw), _st()))
+    return x
+
+
+def lora_down(x: torch.Tensor, a_pack, parts: int, r: int, p: float, seed: int, rng_stream: int, draw: int) -> torch.Tensor:
+    """``t[rows, parts * r]`` fp16, column block j = ``(mask_j * x) @ A_j.T / (1 - p)``: ``x`` fp16 ``[rows, cin]``, ``a_pack`` the
+    PackedWeight of the stacked ``[parts * r, cin]`` A.  ``p == 0`` has no mask to draw: it is ``ops.linear`` itself."""
+    assert x.is_cuda and x.dtype == torch.float16 and x.dim() == 2 and x.stride(1) == 1
+    rows, cin = x.shape
+    assert a_pack.n == parts * r and a_pack.cin == cin and a_pack.taps == 1, (a_pack.n, a_pack.cin, parts, r, cin)
+    if p == 0.0:
+        from . import ops
+        return ops.linear(x, a_pack, out_dtype=torch.float16)
+    t = torch.empty((rows, parts * r), dtype=torch.float16, device=x.device)
+    check(_L().astts_train_lora_down(x.data_ptr(), x.stride(0), a_pack.data.data_ptr(), a_pack.cin_pad, t.data_ptr(), t.stride(0), rows, cin,
+                                     parts, r, float(p), int(seed), int(rng_stream), int(draw), _st()))
+    return t
+
+
+def lora_grad_dropout(u: torch.Tensor, x: torch.Tensor, parts: int, r: int, p: float, seed: int, rng_stream: int, draw: int,
+                      out: Optional[torch.Tensor] = None, alpha: float = 1.0, accumulate: bool = False) -> torch.Tensor:
+    """``lora_grad`` with ``u`` ``[rows, parts * r]`` and the dropout masks applied to ``x`` ``[rows, cin]`` as it is read: rows
+    ``j * r .. (j + 1) * r`` of the result see mask j, and ``alpha / (1 - p)`` scales it."""
+    assert u.is_cuda and u.dim() == 2 and x.dim() == 2 and u.shape[0] == x.shape[0] and u.stride(1) == 1 and x.stride(1) == 1
+    assert u.dtype in (torch.float16, torch.float32) and x.dtype == torch.float16, (u.dtype, x.dtype)
+    rows, n = u.shape
+    cin = x.shape[1]
+    assert n == parts * r, (n, parts, r)
+    if out is None:
+        assert not accumulate
+        out = torch.empty((n, cin), dtype=torch.float32, device=u.device)
+    assert out.dtype == torch.float32 and out.shape == (n, cin) and out.stride(1) == 1
+    ws = _ws(_L().astts_train_lora_grad_workspace_bytes(rows, n, cin), u.device)
+    check(_L().astts_train_lora_grad_dropout(u.data_ptr(), 1 if u.dtype == torch.float32 else 0, u.stride(0), x.data_ptr(), x.stride(0),
+                                             out.data_ptr(), out.stride(0), rows, parts, r, cin, float(alpha), 1 if accumulate else 0,
+                                             float(p), int(seed), int(rng_stream), int(draw), ws.data_ptr(), ws.numel(), _st()))
+    return out
+
+
+def lora_dx_dropout(dt: torch.Tensor, at_pack, residual: torch.Tensor, parts: int, r: int, p: float, seed: int, rng_stream: int,
+                    draw: int, out_dtype=torch.float32) -> torch.Tensor:
+    """``dx = residual + sum_j mask_j * (dt_j @ A_j) / (1 - p)``: ``dt`` fp16 ``[rows, parts * r]``, ``at_pack`` the PackedWeight of the
+    transposed stack ``[cin, parts * r]``, ``residual`` fp32 ``[rows, cin]``.  fp32 output overwrites ``residual``; fp16 is a new tensor."""
+    assert dt.is_cuda and dt.dtype == torch.float16 and dt.dim() == 2 and dt.stride(1) == 1
+    rows, n = dt.shape
+    cin = at_pack.n
+    assert n == parts * r and at_pack.cin == n and at_pack.taps == 1, (n, parts, r, at_pack.cin)
+    assert residual.dtype == torch.float32 and residual.shape == (rows, cin) and residual.is_contiguous()
+    assert out_dtype in (torch.float32, torch.float16)
+    out = residual if out_dtype == torch.float32 else torch.empty((rows, cin), dtype=torch.float16, device=dt.device)
+    check(_L().astts_train_lora_dx_dropout(dt.data_ptr(), dt.stride(0), at_pack.data.data_ptr(), at_pack.cin_pad, residual.data_ptr(),
+                                           out.data_ptr(), 1 if out_dtype == torch.float16 else 0, rows, cin, parts, r, float(p), int(seed),
+                                           int(rng_stream), int(draw), _st()))
+    return out

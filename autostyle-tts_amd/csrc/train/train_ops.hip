@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdarg>
 
+#include "philox.h"
 #include "train_common.h"
 
 namespace astts_train {
@@ -104,6 +105,57 @@ __global__ __launch_bounds__(64) void lora_grad_partial(const void* __restrict__
             bf[j] = b;
         }
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bf, acc, 0, 0, 0);
+    }
+    if (kk < k) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int ni = n0 + mfma_row(e, hh);
+            if (ni < n) part[((int64_t)blockIdx.z * n + ni) * k + kk] = acc[e];
+        }
+    }
+}
+
+// The same product with LoRA dropout's masks regenerated on X as it is read (philox.h): G row n belongs to part n / r and sees X
+// under that part's mask.  A lane holds one column of X over 8 rows, a dropout group is 8 columns of one row: the 8 lanes that share
+// a group column each draw one row's group and hand the bits round.  A tile that spans several parts (r < 32) takes one MFMA per
+// part, U's other columns zeroed.  Same slabs, same planes, same merge.
+template <bool UF32>
+__global__ __launch_bounds__(64) void lora_grad_dropout_partial(const void* __restrict__ u_, int64_t ldu, const _Float16* __restrict__ x, int64_t ldx,
+                                                                float* __restrict__ part, int64_t rows, int n, int k, int r, uint32_t stream,
+                                                                drop_key key) {
+    const int lane = threadIdx.x, c = lane & 31, hh = lane >> 5;
+    const int n0 = blockIdx.x * 32, k0 = blockIdx.y * 32;
+    const int64_t r0 = (int64_t)blockIdx.z * LG_ROWS, r1 = min(rows, r0 + (int64_t)LG_ROWS);
+    const int nn = n0 + c, kk = k0 + c;
+    const int j0 = n0 / r, j1 = (min(n, n0 + 32) - 1) / r;                    // the parts this tile has rows of
+    float16v acc;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+    for (int64_t rr = r0; rr < r1; rr += 16) {
+        half8 af, bf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t row = rr + 8 * hh + j;
+            const bool ok = row < r1;
+            _Float16 a = (_Float16)0.0f, b = (_Float16)0.0f;
+            if (ok && nn < n) a = UF32 ? (_Float16) reinterpret_cast<const float*>(u_)[row * ldu + nn] : reinterpret_cast<const _Float16*>(u_)[row * ldu + nn];
+            if (ok && kk < k) b = x[row * ldx + kk];
+            af[j] = a;
+            bf[j] = b;
+        }
+        const uint64_t group = ((uint64_t)(rr + 8 * hh + (c & 7)) * (uint64_t)k + (uint64_t)(k0 + (c & ~7))) >> 3;
+        for (int jp = j0; jp <= j1; ++jp) {
+            half8 am, bm;
+            const uint32_t mine = key.thr ? dropout_keep_bits(key, group, stream + jp) : 0xFFu;
+            const bool in_part = nn >= jp * r && nn < (jp + 1) * r;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t bits = __shfl(mine, (lane & ~7) | j, 64);
+                bm[j] = (bits >> (c & 7) & 1u) ? bf[j] : (_Float16)0.0f;
+                am[j] = in_part ? af[j] : (_Float16)0.0f;
+            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(am, bm, acc, 0, 0, 0);
+        }
     }
     if (kk < k) {
 #pragma unroll
@@ -231,6 +283,39 @@ int astts_train_lora_grad(const void* u, int32_t u_f32, int64_t ldu, const void*
     TRAIN_CHECK_LAUNCH();
     hipLaunchKernelGGL(lora_grad_merge, dim3((unsigned)cdiv((int64_t)n * k, 256)), dim3(256), 0, (hipStream_t)stream, part, g, ldg, n, k,
                        (int)slabs, alpha, accumulate);
+    TRAIN_CHECK_LAUNCH();
+    return ASTTS_OK;
+}
+
+int astts_train_lora_grad_dropout(const void* u, int32_t u_f32, int64_t ldu, const void* x_f16, int64_t ldx, float* g, int64_t ldg,
+                                  int64_t rows, int32_t parts, int32_t r, int32_t cin, float alpha, int32_t accumulate, double p,
+                                  int64_t seed, uint32_t rng_stream, uint32_t draw, void* workspace, size_t workspace_bytes,
+                                  astts_stream_t stream) {
+    TRAIN_REQUIRE(u && x_f16 && g && rows > 0 && cin > 0 && cin % 8 == 0 && parts >= 1 && parts <= 3 && r >= 8 && r <= 64 && r % 8 == 0,
+                  ASTTS_ERR_INVALID, "lora_grad_dropout: bad arguments (rows %lld cin %d: a multiple of 8; parts %d in 1..3; r %d: a multiple of 8 up to 64)",
+                  (long long)rows, cin, parts, r);
+    const int n = parts * r, k = cin;
+    TRAIN_REQUIRE(ldu >= n && ldx >= k && ldg >= k, ASTTS_ERR_INVALID, "lora_grad_dropout: row strides (ldu %lld ldx %lld ldg %lld) must cover the rows",
+                  (long long)ldu, (long long)ldx, (long long)ldg);
+    TRAIN_REQUIRE(p >= 0.0 && p < 1.0, ASTTS_ERR_INVALID, "lora_grad_dropout: p = %g is outside [0, 1)", p);
+    const int64_t slabs = cdiv(rows, LG_ROWS);
+    TRAIN_REQUIRE(slabs <= 65535 && cdiv(k, 32) <= 65535, ASTTS_ERR_INVALID, "lora_grad_dropout: %lld rows / cin %d exceed the grid", (long long)rows, k);
+    TRAIN_REQUIRE(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= astts_train_lora_grad_workspace_bytes(rows, n, k),
+                  ASTTS_ERR_WORKSPACE, "lora_grad_dropout: workspace of %zu bytes, %zu needed (16-byte aligned)", workspace_bytes,
+                  astts_train_lora_grad_workspace_bytes(rows, n, k));
+    drop_key key;
+    key.seed_lo = (uint32_t)(uint64_t)seed, key.seed_hi = (uint32_t)((uint64_t)seed >> 32), key.draw = draw, key.thr = (uint32_t)(p * 65536.0);
+    const dim3 grid((unsigned)cdiv(n, 32), (unsigned)cdiv(k, 32), (unsigned)slabs);
+    float* part = (float*)workspace;
+    if (u_f32)
+        hipLaunchKernelGGL(lora_grad_dropout_partial<true>, grid, dim3(64), 0, (hipStream_t)stream, u, ldu, (const _Float16*)x_f16, ldx, part, rows, n, k,
+                           r, rng_stream, key);
+    else
+        hipLaunchKernelGGL(lora_grad_dropout_partial<false>, grid, dim3(64), 0, (hipStream_t)stream, u, ldu, (const _Float16*)x_f16, ldx, part, rows, n, k,
+                           r, rng_stream, key);
+    TRAIN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(lora_grad_merge, dim3((unsigned)cdiv((int64_t)n * k, 256)), dim3(256), 0, (hipStream_t)stream, part, g, ldg, n, k,
+                       (int)slabs, (float)((double)alpha / (1.0 - p)), accumulate);
     TRAIN_CHECK_LAUNCH();
     return ASTTS_OK;
 }

@@ -15,6 +15,8 @@
 extern "C" {
 #endif
 
+/* Stays 1: the version counts changes that break a caller.  The regulariser entry points at the end of this header were added under
+ * it; every earlier prototype is unchanged. */
 #define ASTTS_TRAIN_ABI_VERSION 1
 
 int32_t astts_train_abi_version(void);
@@ -66,6 +68,50 @@ int astts_train_sumsq(const float* x, int64_t n, float* out, void* workspace, si
  * once, as torch.optim.AdamW forms them; the element-wise arithmetic is fp32. */
 int astts_train_adamw(float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
                       double weight_decay, double bias_corr1, double bias_corr2, double grad_mul, astts_stream_t stream);
+
+/* ---- The regularisers of the reference's recipe: LoRA dropout and NEFTune, from a counter-based generator (csrc/train/philox.h).
+ * Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, ten rounds); no state, no atomics, no
+ * stored masks -- a mask is regenerated wherever it is consumed.
+ *   key     = the 64 bits of `seed`, low word then high word
+ *   counter = (group low word, group high word, rng_stream, draw)
+ *   rng_stream = layer * 8 + the projection's position in astts.llm.peft.PROJ for dropout (part j of a fused call uses
+ *             rng_stream + j: the projections that share an input are neighbours in PROJ), 0xFFFFFFFF for NEFTune
+ *   draw    = the number of training forwards run before this one (one per micro-batch, skipped steps included)
+ * Dropout: a group is 8 consecutive columns of one row of the [rows, cin] input, group = (row * cin + col) / 8 (cin a multiple of
+ * 8); element e of the group takes 16 bits of output word e >> 1, the low half when e is even, the high half when e is odd, and is
+ * kept iff those bits are >= floor(p * 65536).  The scale 1 / (1 - p) multiplies fp32 accumulators, never an fp16 operand.
+ * NEFTune: a group is 4 consecutive fp32 elements, element i uses word i & 3 of group i >> 2: u = ((bits >> 8) + 0.5) * 2^-24,
+ * x += mag * (2 u - 1).  0 <= p < 1 everywhere; p = 0 keeps every element. */
+
+/* The keep mask of one (seed, rng_stream, draw, p) as uint8 [rows, cin] (1 = kept).  The test hook that pins the generator. */
+int astts_train_dropout_mask(void* mask_u8, int64_t rows, int32_t cin, double p, int64_t seed, uint32_t rng_stream, uint32_t draw,
+                             astts_stream_t stream);
+
+/* In place on the fp32 [rows, hidden] embedding output (hidden a multiple of 4): x += mag * (2 u - 1); the caller forms
+ * mag = alpha / sqrt(T * hidden), T the micro-batch's padded length (trl's neftune_post_forward_hook; padding rows get noise too). */
+int astts_train_neftune(float* x, int64_t rows, int32_t hidden, float mag, int64_t seed, uint32_t draw, astts_stream_t stream);
+
+/* t[rows, parts * r] (fp16, row stride ldt): column block j = (mask_j o x) A_j^T / (1 - p).  x: fp16 [rows, cin] (row stride ldx);
+ * a: the stacked fp16 [parts * r, cin] (row stride lda); parts <= 3, r a multiple of 8 up to 64; strides multiples of 8.  Every x
+ * fragment is read once and masked per part in registers; v_mfma_f32_32x32x16_f16, fp32 accumulation, one rounding at the store. */
+int astts_train_lora_down(const void* x_f16, int64_t ldx, const void* a_f16, int64_t lda, void* t_f16, int64_t ldt, int64_t rows,
+                          int32_t cin, int32_t parts, int32_t r, double p, int64_t seed, uint32_t rng_stream, uint32_t draw,
+                          astts_stream_t stream);
+
+/* astts_train_lora_grad with n = parts * r, k = cin and the masks applied to X as it is read: rows j * r .. (j + 1) * r of G use
+ * mask j, and alpha / (1 - p) scales the merged sum.  The same row slabs, workspace (astts_train_lora_grad_workspace_bytes(rows,
+ * parts * r, cin)) and slab-order merge: bit-for-bit repeatable. */
+int astts_train_lora_grad_dropout(const void* u, int32_t u_f32, int64_t ldu, const void* x_f16, int64_t ldx, float* g, int64_t ldg,
+                                  int64_t rows, int32_t parts, int32_t r, int32_t cin, float alpha, int32_t accumulate, double p,
+                                  int64_t seed, uint32_t rng_stream, uint32_t draw, void* workspace, size_t workspace_bytes,
+                                  astts_stream_t stream);
+
+/* dx[rows, cin] = residual + (1 / (1 - p)) * sum_j mask_j o (dt_j A_j), the masks applied in the epilogue.  dt: fp16
+ * [rows, parts * r] (row stride lddt); at: the TRANSPOSED stack, fp16 [cin, parts * r] (row stride ldat); residual: fp32 [rows, cin]
+ * contiguous; dx: fp32 (may be the residual itself) or fp16 (dx_f16 = 1) [rows, cin] contiguous.  One pass, 16-byte accesses. */
+int astts_train_lora_dx_dropout(const void* dt_f16, int64_t lddt, const void* at_f16, int64_t ldat, const float* residual, void* dx,
+                                int32_t dx_f16, int64_t rows, int32_t cin, int32_t parts, int32_t r, double p, int64_t seed,
+                                uint32_t rng_stream, uint32_t draw, astts_stream_t stream);
 
 #ifdef __cplusplus
 }
