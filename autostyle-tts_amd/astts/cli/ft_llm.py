@@ -12,7 +12,8 @@ existed); the reference's own values are ``--lr_scheduler linear`` (scripts/trai
 trl's ConstantLengthDataset -- conversations concatenated in file order and cut into chunks of exactly max_seq_len tokens that attend
 across conversation boundaries).  An ``--lr_scheduler`` this command does not know is an error, not a silently constant rate.
 What the reference does and this does not (NF4 base, bf16, gradient checkpointing, embedding resize, checkpoint resume, the
-evaluation every 50 steps with load_best_model_at_end, multi-GPU, Qwen): DESIGN.md section 2.
+evaluation every 50 steps with load_best_model_at_end, multi-GPU): DESIGN.md section 2.  The base may be a Llama or a Qwen2
+checkpoint directory (src/ft_llm_cn.py's Qwen2.5: q / k / v biases, plain RoPE); its config.json decides.
 
 Writes ``{output_folder}/{ft_model_id}``: the peft adapter directory (adapter_config.json, adapter_model.safetensors) and
 ``train_log.jsonl`` (one line per optimizer step: step, loss, grad_norm, lr, loss_scale, skipped)."""
@@ -128,12 +129,8 @@ def load_base(args):
     from astts.llm.weights import load_llama_weights, make_llama_weights
     base = args.base_model_path or args.base_model_id
     if base and os.path.isdir(base):
-        tok = None
-        try:
-            from transformers import AutoTokenizer
-            tok = AutoTokenizer.from_pretrained(base)
-        except Exception as e:  # noqa: BLE001
-            print(f"Warning: no tokenizer under '{base}' ({e}); using the hash stand-in")
+        from astts.cli.search_milvus import load_tokenizer
+        tok = load_tokenizer(base)
         state = load_llama_weights(base)
         return state, shape_from_config(base, int(state["model.embed_tokens.weight"].shape[0])), tok, base
     if not (args.allow_random_init or os.environ.get("ASTTS_ALLOW_RANDOM_INIT") == "1"):

@@ -182,6 +182,8 @@ def main(args, client=None, embedder=None):
                 from astts.cli.search_milvus import load_embedder
                 embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed,
                                          getattr(args, "base_model_path", None), getattr(args, "llm_precision", None))
+            from astts.cli.search_milvus import check_query_dim
+            check_query_dim(client, args.collection_name, 2 * embedder.cfg.hidden)
             bios = load_biographies(getattr(args, "biography_json", ""))
         if getattr(args, "generate_biographies", False):
             # rank 0 samples the biographies of the speakers the file does not cover (all rows' speakers, not its shard's) and every

@@ -23,29 +23,43 @@ speaker_bio = {
 }
 
 
+TOKENIZER_FILES = ("tokenizer.json", "tokenizer.model", "vocab.json", "tokenizer_config.json")
+
+
+def load_tokenizer(model_path):
+    """The checkpoint's own tokenizer when the directory has one and transformers can read it, else None (the caller then uses the hash
+    stand-in).  The files are looked for first: for some model types (qwen2) AutoTokenizer builds an EMPTY tokenizer from config.json
+    alone, without an error, and every text would encode to no tokens."""
+    import os
+
+    try:
+        if not any(os.path.isfile(os.path.join(model_path, f)) for f in TOKENIZER_FILES):
+            raise FileNotFoundError("none of " + ", ".join(TOKENIZER_FILES))
+        from transformers import AutoTokenizer
+
+        return AutoTokenizer.from_pretrained(model_path)
+    except Exception as e:  # noqa: BLE001
+        print(f"Warning: no tokenizer under '{model_path}' ({e}); using the hash stand-in")
+        return None
+
+
 def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=None, precision=None):
     """:36-72 ``load_model_and_tokenizer``: the checkpoint directory must exist (safetensors / .bin shards + tokenizer).
     A PEFT LoRA adapter directory (adapter_config.json: what the reference retrieves with) loads over its base checkpoint
     (``base_model_path``, else the adapter's base_model_name_or_path as a local directory or hub-cache snapshot; never fetched) and
     runs LLM.int8 + the unmerged LoRA branch, the reference's numerics; a merged checkpoint runs fp16.  ``precision`` ("int8" /
-    "fp16") overrides either default.  Without a directory this raises unless random-init weights are explicitly allowed
+    "fp16") overrides either default.  The shape comes from the directory's config.json (Llama or Qwen2; astts.llm.peft.shape_from_config).  Without a directory this raises unless random-init weights are explicitly allowed
     (plumbing runs, benchmarks)."""
     import os
 
     from astts.llm.config import LlamaShape
     from astts.llm.embedder import LlamaEmbedder
-    from astts.llm.peft import is_adapter_dir, load_peft_model
+    from astts.llm.peft import is_adapter_dir, load_peft_model, shape_from_config
     from astts.llm.weights import load_llama_weights, make_llama_weights
 
     cfg = LlamaShape.llama32_3b()
     if model_path and os.path.isdir(model_path):
-        tok = None
-        try:  # the checkpoint's own tokenizer when transformers can read it
-            from transformers import AutoTokenizer
-
-            tok = AutoTokenizer.from_pretrained(model_path)
-        except Exception as e:  # noqa: BLE001
-            print(f"Warning: no tokenizer under '{model_path}' ({e}); using the hash stand-in")
+        tok = load_tokenizer(model_path)
         if is_adapter_dir(model_path):
             if tok is not None and getattr(tok, "pad_token", None) is None and hasattr(tok, "eos_token"):
                 tok.pad_token = tok.eos_token                                   # :47-48 of the reference: pad = eos
@@ -53,6 +67,8 @@ def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=
             int8 = (precision or "int8") == "int8"
             return LlamaEmbedder(state, cfg, tokenizer=tok, int8=int8, lora=adapter)
         state = load_llama_weights(model_path)
+        if os.path.isfile(os.path.join(model_path, "config.json")):      # the checkpoint's own shape (Llama or Qwen2); else the 3.2-3B preset
+            cfg = shape_from_config(model_path, int(state["model.embed_tokens.weight"].shape[0]))
         if (precision or "fp16") == "int8":
             return LlamaEmbedder(state, cfg, tokenizer=tok, int8=True)
         return LlamaEmbedder(state, cfg, tokenizer=tok)
@@ -62,6 +78,18 @@ def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=
         cfg = LlamaShape.tiny()
     print(f"Warning: '{model_path}' not found; seeded RANDOM-INIT Llama weights at {cfg.hidden}-d (explicitly allowed)")
     return LlamaEmbedder(make_llama_weights(cfg, seed), cfg, int8=precision == "int8")
+
+
+def check_query_dim(client, collection_name, query_dim):
+    """The query is 2 x the embedder's hidden size (6144 for Llama-3.2-3B, 7168 for Qwen2.5-7B); a bank built with another model cannot
+    be searched with it.  One message with both numbers instead of the search's byte count."""
+    if not hasattr(client, "get_collection_info") or not client.has_collection(collection_name=collection_name):
+        return                                  # a missing collection is reported where it is searched
+    fields = client.get_collection_info(collection_name).get("fields", [])
+    bank_dim = next((int(f["params"]["dim"]) for f in fields if "dim" in (f.get("params") or {})), None)
+    if bank_dim is not None and bank_dim != int(query_dim):
+        raise SystemExit(f"the query embedding has {int(query_dim)} dimensions (2 x the LLM's hidden size {int(query_dim) // 2}) but collection "
+                         f"'{collection_name}' holds {bank_dim}-dimensional vectors: this bank was built with another model")
 
 
 def emb_text_bio(speaker, embedder):
@@ -103,6 +131,7 @@ def main(args, embedder=None):
         print(f"Error retrieving collection info: {e}")
         traceback.print_exc()
         return None
+    check_query_dim(client, collection_name, 2 * embedder.cfg.hidden)
     query_text = args.search_text
     try:
         emotion_emb = embedder.get_embedding(query_text)                     # :214

@@ -1,5 +1,6 @@
 """Shapes of the embedder LLM.  The reference loads "Llama 3.2" 3B (src/search_milvus.py:251-252, milvus/RAG.py:458:
-hidden 3072 -> 2 x 3072 = the 6144-d bank); these are that checkpoint's config.json values."""
+hidden 3072 -> 2 x 3072 = the 6144-d bank); these are that checkpoint's config.json values.  The same dataclass describes a Qwen2
+checkpoint (the reference's ``_cn`` scripts run Qwen2.5-7B-Instruct): ``model_type``, ``qkv_bias`` and ``rope_type`` carry the differences."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -26,6 +27,9 @@ class LlamaShape:
     eos_token_id: int = 128001
     bos_token_id: int = 128000
     eos_token_ids: tuple = ()   # further stop ids (generation_config.json's list; set by the adapter loader)
+    model_type: str = "llama"   # "llama" | "qwen2": the transformers class a checkpoint of this shape loads into
+    qkv_bias: bool = False      # q / k / v projections carry a bias (Qwen2; Llama's attention_bias)
+    rope_type: str = "llama3"   # "llama3": the scaling above; "default": plain 1 / theta^(2i/d), the four rope_* fields unused
 
     @staticmethod
     def llama32_3b() -> "LlamaShape":
@@ -41,6 +45,33 @@ class LlamaShape:
         """The real widths (hidden 3072, 24 / 8 heads, FFN 8192) with few layers and a small vocabulary: the kernels at the
         shapes Llama-3.2-3B runs them at, in a model whose weights regenerate from a seed in seconds."""
         return LlamaShape(vocab=4096, layers=3, eos_token_id=2, bos_token_id=1)
+
+    @staticmethod
+    def qwen2_tiny() -> "LlamaShape":
+        """Qwen2.5-7B's differences from Llama in their smallest form: q / k / v biases, plain RoPE at theta 1e6, an untied head and a
+        GQA group of 7 (7 query heads on 1 KV head).  896 and 1152 are multiples of 128 and 64 but not of 256."""
+        return LlamaShape(vocab=512, hidden=896, layers=3, heads=7, kv_heads=1, ffn=1152, rms_eps=1e-6, rope_theta=1e6,
+                          max_positions=32768, tie_embeddings=False, eos_token_id=2, bos_token_id=1, model_type="qwen2", qkv_bias=True,
+                          rope_type="default")
+
+    def hf_config(self):
+        """The transformers config of this shape: Qwen2Config or LlamaConfig (used only by tests/golden/make_qwen2_fixtures.py)."""
+        if self.model_type == "qwen2":
+            from transformers import Qwen2Config
+
+            assert self.qkv_bias and self.rope_type == "default" and self.hidden == self.heads * self.head_dim, self
+            return Qwen2Config(vocab_size=self.vocab, hidden_size=self.hidden, intermediate_size=self.ffn, num_hidden_layers=self.layers,
+                               num_attention_heads=self.heads, num_key_value_heads=self.kv_heads, max_position_embeddings=self.max_positions,
+                               rms_norm_eps=self.rms_eps, rope_theta=self.rope_theta, rope_scaling=None, use_sliding_window=False,
+                               tie_word_embeddings=self.tie_embeddings, hidden_act="silu", attention_dropout=0.0,
+                               eos_token_id=self.eos_token_id, bos_token_id=self.bos_token_id, pad_token_id=None)
+        from transformers import LlamaConfig
+
+        kw = self.hf_kwargs()
+        kw["attention_bias"] = self.qkv_bias
+        if self.rope_type == "default":
+            kw["rope_scaling"] = None
+        return LlamaConfig(**kw)
 
     def hf_kwargs(self) -> dict:
         """transformers.LlamaConfig arguments (used only by tests/golden/make_llama_fixtures.py)."""

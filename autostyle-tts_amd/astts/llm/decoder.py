@@ -9,6 +9,9 @@ the seven projections of every layer become int8 weights with per-row scales, th
 columns of each sequence (|x| >= ``int8_threshold``) kept in fp16 against the dequantised weight, and the adapter's LoRA branch
 (``lora``: an astts.llm.peft.LoraAdapter) runs unmerged in fp32 -- all of it csrc/ops_int8.hip (DESIGN.md "LLM.int8 + LoRA").
 No fp16 copy of those projections is kept.  A ``lora`` without ``int8`` is merged into the fp16 weights at load.
+
+A Qwen2 shape (``cfg.qkv_bias``, ``cfg.rope_type == "default"``, untied head; DESIGN.md section 2 "Qwen2") runs through the same stack:
+the q | k | v bias rides on the fused pack into the GEMM's fp32 epilogue, in both layouts and both precisions.
 """
 from __future__ import annotations
 
@@ -37,6 +40,20 @@ def llama3_inv_freq(cfg: LlamaShape) -> torch.Tensor:
     return torch.where(medium, smoothed, inv_l)
 
 
+def default_inv_freq(cfg: LlamaShape) -> torch.Tensor:
+    """transformers' compute_default_rope_parameters: 1 / theta^(2i/d), float32 as there."""
+    return 1.0 / (cfg.rope_theta ** (torch.arange(0, cfg.head_dim, 2, dtype=torch.float) / cfg.head_dim))
+
+
+def inv_freq(cfg: LlamaShape) -> torch.Tensor:
+    """The RoPE inverse frequencies ``cfg.rope_type`` names."""
+    if cfg.rope_type == "llama3":
+        return llama3_inv_freq(cfg)
+    if cfg.rope_type == "default":
+        return default_inv_freq(cfg)
+    raise ValueError(f"rope_type {cfg.rope_type!r}: 'llama3' or 'default'")
+
+
 def _merge_lora(state: dict, lora) -> dict:
     """W + scaling * B A in fp32 for the fp16 path (the int8 path keeps the branch unmerged, as peft does)."""
     out = dict(state)
@@ -56,20 +73,27 @@ class LlamaDecoder:
         self.device = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.mfma_attention = os.environ.get("ASTTS_LLM_ATTN", "mfma") != "valu"
         self.int8, self.int8_threshold = bool(int8), float(int8_threshold)
+        # a bias this model would drop is an error: the checkpoint would run and compute another function
+        ok = (".q_proj.bias", ".k_proj.bias", ".v_proj.bias") if cfg.qkv_bias else ()
+        dropped = [k for k in state if k.endswith(".bias") and not (ok and k.endswith(ok))]
+        if dropped:
+            raise ValueError(f"the checkpoint has biases that this {cfg.model_type} shape (qkv_bias={cfg.qkv_bias}) does not apply: {dropped[:3]}")
         if lora is not None and not self.int8:
             state = _merge_lora(state, lora)
 
         def weight(i: int, *names: str):
             """The projections ``names`` of layer i, fused along their output rows, in the format this model runs."""
             ws = [state[f"model.layers.{i}.{nm}.weight"] for nm in names]
+            # Qwen2: q | k | v carry a bias, added in fp32 in the GEMM's epilogue (before the fp16 store, so before RoPE); a missing one is an error
+            bias = torch.cat([state[f"model.layers.{i}.{nm}.bias"].float() for nm in names]) if cfg.qkv_bias and "q_proj" in names[0] else None
             if not self.int8:
-                return ops.PackedWeight(ws[0] if len(ws) == 1 else torch.cat(ws, 0), None, dev)
+                return ops.PackedWeight(ws[0] if len(ws) == 1 else torch.cat(ws, 0), bias, dev)
             ab = [None if lora is None else lora.pairs.get((i, nm.split(".")[-1])) for nm in names]
             r = next((p[0].shape[0] for p in ab if p is not None), None)
             if r is not None:                                 # a fused projection with LoRA on some parts: zero pairs on the others
                 ab = [p if p is not None else (torch.zeros(r, w.shape[1]), torch.zeros(w.shape[0], r)) for w, p in zip(ws, ab)]
             return ops.Int8Weight([(w, None, None) if p is None else (w, p[0], p[1]) for w, p in zip(ws, ab)],
-                                  1.0 if lora is None else lora.scaling, dev)
+                                  1.0 if lora is None else lora.scaling, dev, bias=bias)
 
         with torch.cuda.device(dev):
             f = lambda k: state[k].to(device=dev, dtype=torch.float32).contiguous()
@@ -105,7 +129,7 @@ class LlamaDecoder:
 
     def _rope_tables(self, n: int) -> None:
         """(cos, sin) rows for positions < n, published as ONE tuple: a thread that sees the new cos also sees the new sin."""
-        fr = torch.arange(n, dtype=torch.float32)[:, None] * llama3_inv_freq(self.cfg)[None, :]
+        fr = torch.arange(n, dtype=torch.float32)[:, None] * inv_freq(self.cfg)[None, :]
         self._rope = (fr.cos().to(self.device).contiguous(), fr.sin().to(self.device).contiguous())
 
     def _rope_for(self, n: int):

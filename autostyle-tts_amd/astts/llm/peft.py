@@ -168,11 +168,28 @@ def resolve_base(adapter: LoraAdapter, base_model_path: Optional[str] = None) ->
                             f"snapshot); download it yourself and pass --base_model_path <dir>")
 
 
+class ConfigError(ValueError):
+    """A config.json this port refuses to run (and which key says so)."""
+
+
 def shape_from_config(base_dir: str, vocab: Optional[int] = None) -> LlamaShape:
-    """LlamaShape from a transformers config.json (``vocab``: the row count of the embedding table in use)."""
+    """LlamaShape from a transformers config.json (``vocab``: the row count of the embedding table in use).  ``model_type`` llama or
+    qwen2; RoPE plain (no ``rope_scaling``) or Llama-3 scaled.  Anything that would run but compute another model is refused by key."""
     with open(os.path.join(base_dir, "config.json")) as f:
         c = json.load(f)
-    rs = c.get("rope_scaling") or {}
+    model_type = str(c.get("model_type", "llama"))
+    if model_type not in ("llama", "qwen2"):
+        raise ConfigError(f"config.json model_type={model_type!r}: only 'llama' and 'qwen2' checkpoints are supported")
+    if c.get("use_sliding_window"):
+        raise ConfigError("config.json use_sliding_window=true: sliding-window attention is not built")
+    if c.get("mlp_bias"):
+        raise ConfigError("config.json mlp_bias=true: biases on the MLP projections are not built")
+    rp = c.get("rope_parameters") if isinstance(c.get("rope_parameters"), dict) else {}      # transformers >= 5: theta and scaling in one
+    rs_key = "rope_scaling" if c.get("rope_scaling") else "rope_parameters"
+    rs = c.get("rope_scaling") or rp
+    kind = str(rs.get("rope_type", rs.get("type", "default")))
+    if kind not in ("default", "llama3"):
+        raise ConfigError(f"config.json {rs_key} type {kind!r}: only plain RoPE (no rope_scaling) and 'llama3' scaling are built")
     d = LlamaShape()
     heads = int(c["num_attention_heads"])
     eos = c.get("eos_token_id", d.eos_token_id)
@@ -180,13 +197,15 @@ def shape_from_config(base_dir: str, vocab: Optional[int] = None) -> LlamaShape:
     return LlamaShape(vocab=int(vocab or c["vocab_size"]), hidden=int(c["hidden_size"]), layers=int(c["num_hidden_layers"]), heads=heads,
                       kv_heads=int(c.get("num_key_value_heads", heads)), head_dim=int(c.get("head_dim") or c["hidden_size"] // heads),
                       ffn=int(c["intermediate_size"]), rms_eps=float(c.get("rms_norm_eps", d.rms_eps)),
-                      rope_theta=float(c.get("rope_theta", d.rope_theta)), rope_factor=float(rs.get("factor", d.rope_factor)),
+                      rope_theta=float(c.get("rope_theta", rp.get("rope_theta", d.rope_theta))), rope_factor=float(rs.get("factor", d.rope_factor)),
                       rope_low_freq_factor=float(rs.get("low_freq_factor", d.rope_low_freq_factor)),
                       rope_high_freq_factor=float(rs.get("high_freq_factor", d.rope_high_freq_factor)),
                       rope_original_max_pos=int(rs.get("original_max_position_embeddings", d.rope_original_max_pos)),
                       max_positions=int(c.get("max_position_embeddings", d.max_positions)),
                       tie_embeddings=bool(c.get("tie_word_embeddings", d.tie_embeddings)), eos_token_id=int(eos_l[0]),
-                      bos_token_id=int(c.get("bos_token_id", d.bos_token_id) if c.get("bos_token_id") is not None else d.bos_token_id))
+                      bos_token_id=int(c.get("bos_token_id", d.bos_token_id) if c.get("bos_token_id") is not None else d.bos_token_id),
+                      model_type=model_type, qkv_bias=True if model_type == "qwen2" else bool(c.get("attention_bias", False)),
+                      rope_type=kind)
 
 
 def generation_eos_ids(base_dir: str) -> Tuple[int, ...]:

@@ -8,7 +8,8 @@ an input).  Backward: dX of every frozen projection is ``ops.linear`` on the tra
 norms, SwiGLU, the softmax gradient, the LoRA weight gradients and the optimizer are csrc/train/*.hip (astts.train_ops); RoPE's
 transpose is the RoPE kernel with a negated sine table.  fp16 where a tensor is an MFMA operand, fp32 for the residual stream, its
 gradient, the LoRA masters, their gradients and the Adam moments; a static power-of-two loss scale keeps the fp16 gradients in
-range.  No atomics: a step is bit-for-bit repeatable.
+range.  No atomics: a step is bit-for-bit repeatable.  A Qwen2 base (``cfg.qkv_bias``): the q | k | v bias is frozen; the forward picks
+it up with the decoder's packs (the base GEMM's epilogue), the transposed packs of the backward carry none, so dX, dA and dB do not see it.
 
 Regularisers (``lora_dropout``, ``neftune_alpha``; both 0 = the path above, bit for bit).  peft gives every LoRA module its own
 dropout on its input, so q, k and v mask the same ``h1`` independently; the masks are never stored: each is a function of

@@ -11,6 +11,7 @@ import torch
 from .config import LlamaShape
 
 StateDict = Dict[str, torch.Tensor]
+BIAS_OUTLIERS = (3, 40, 77, 101, 126)    # the entries (mod the bias length) of every q / k bias that make_llama_weights sets to +-16
 
 
 def make_llama_weights(cfg: LlamaShape, seed: int = 0, device=None) -> StateDict:
@@ -37,6 +38,17 @@ def make_llama_weights(cfg: LlamaShape, seed: int = 0, device=None) -> StateDict
     sd["model.norm.weight"] = 1.0 + r(cfg.hidden, std=0.1)
     if not cfg.tie_embeddings:
         sd["lm_head.weight"] = r(cfg.vocab, cfg.hidden, std=0.05)
+    if cfg.qkv_bias:
+        # drawn after everything else, so a shape without biases consumes the generator exactly as before.  Real Qwen2.5 q / k biases
+        # have large outliers: std 0.5 and a fixed handful of entries at +-16, values that matter after the fp16 store of q | k | v
+        for i in range(cfg.layers):
+            p = f"model.layers.{i}."
+            for nm, n, std in (("q", q, 0.5), ("k", kv, 0.5), ("v", kv, 0.05)):
+                b = r(n, std=std)
+                if nm != "v":
+                    for j, at in enumerate(BIAS_OUTLIERS):
+                        b[at % n] = 16.0 if (i + j) % 2 == 0 else -16.0
+                sd[p + f"self_attn.{nm}_proj.bias"] = b
     return sd
 
 

@@ -911,8 +911,9 @@ def i8_lora_down(x: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
 
 def i8_gemm(act: I8Act, cb: torch.Tensor, scb: torch.Tensor, n: int, outliers: bool = True, t: Optional[torch.Tensor] = None,
             lora_b: Optional[torch.Tensor] = None, r: int = 0, groups=(0, 0), scaling: float = 1.0,
-            residual: Optional[torch.Tensor] = None, out_kind: int = I8_OUT_F32) -> torch.Tensor:
-    """astts_op_i8_gemm on quantised activations: -> ``[m, n]`` fp32 / fp16 / int32 (``out_kind``)."""
+            residual: Optional[torch.Tensor] = None, out_kind: int = I8_OUT_F32, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """astts_op_i8_gemm on quantised activations: -> ``[m, n]`` fp32 / fp16 / int32 (``out_kind``).  ``bias``: fp32 ``[n]``, added in
+    fp32 in the epilogue of the float kinds."""
     m, k_pad = act.ca.shape
     assert cb.shape[1] == k_pad and cb.shape[0] >= _up(n, 128) and scb.numel() >= cb.shape[0]
     dt = {I8_OUT_F32: torch.float32, I8_OUT_F16: torch.float16, I8_OUT_ACC: torch.int32}[out_kind]
@@ -924,20 +925,24 @@ def i8_gemm(act: I8Act, cb: torch.Tensor, scb: torch.Tensor, n: int, outliers: b
     if r > 0:
         assert t is not None and lora_b is not None and lora_b.shape[1] == r and lora_b.shape[0] >= cb.shape[0]
         t, lora_b = _f32(t), _f32(lora_b)
+    if bias is not None:
+        bias = _f32(bias)
+        assert bias.numel() == n and bias.device == act.ca.device, (bias.shape, n)
     g1, g2 = groups
     _lib.check(_L().astts_op_i8_gemm(act.ca.data_ptr(), act.sca.data_ptr(), cb.data_ptr(), scb.data_ptr(), m, n, k_pad,
                                      act.xo.data_ptr() if outliers else None, act.xo.shape[1], act.cols.data_ptr(), act.cnt.data_ptr(),
                                      _p(t) if r > 0 else None, t.shape[1] if r > 0 else 0, _p(lora_b) if r > 0 else None, r, g1, g2,
-                                     float(scaling), _p(residual), ldr, out.data_ptr(), out_kind, n, _st()))
+                                     float(scaling), _p(bias), _p(residual), ldr, out.data_ptr(), out_kind, n, _st()))
     return out
 
 
 class Int8Weight:
     """One quantised projection (LLM.int8) with its LoRA branch, in the layout astts_op_i8_gemm reads.  ``parts``: the fused weights'
     pieces ``[(w [n_i, k], lora_a [r, k] or None, lora_b [n_i, r] or None), ...]`` (q | k | v, gate | up), at most three; every
-    piece but the last has a multiple of 32 rows.  No fp16 copy of the weight is kept."""
+    piece but the last has a multiple of 32 rows.  ``bias``: fp32 ``[n]`` over the fused rows (Qwen2's q | k | v), or None.  No fp16
+    copy of the weight is kept."""
 
-    def __init__(self, parts, scaling: float = 1.0, device=None):
+    def __init__(self, parts, scaling: float = 1.0, device=None, bias: Optional[torch.Tensor] = None):
         device = device or torch.device("cuda", torch.cuda.current_device())
         assert 1 <= len(parts) <= 3
         w = torch.cat([p[0].to(torch.float32) for p in parts], 0) if len(parts) > 1 else parts[0][0]
@@ -952,6 +957,8 @@ class Int8Weight:
         big = 1 << 30
         self.groups = (bounds + [big, big])[:2] if bounds else (big, big)
         self.scaling = float(scaling)
+        assert bias is None or bias.numel() == self.n, (None if bias is None else bias.shape, self.n)
+        self.bias = None if bias is None else bias.to(device=device, dtype=torch.float32).contiguous()
         has = [p[1] is not None for p in parts]
         assert all(has) or not any(has), "Int8Weight: LoRA on some parts of a fused projection only is not supported"
         self.r = 0
@@ -975,6 +982,6 @@ class Int8Weight:
         act = i8_quantize_act(x2, seg, segments, tau)
         t = i8_lora_down(x2, self.lora_a) if self.r else None
         y = i8_gemm(act, self.cb, self.scb, self.n, outliers=tau > 0, t=t, lora_b=self.lora_b if self.r else None, r=self.r,
-                    groups=self.groups, scaling=self.scaling, residual=residual,
+                    groups=self.groups, scaling=self.scaling, residual=residual, bias=self.bias,
                     out_kind=I8_OUT_F16 if out_dtype == torch.float16 else I8_OUT_F32)
         return y.view(*x.shape[:-1], self.n)

@@ -8,7 +8,7 @@
 //   i8_quant_act        X fp16 [M, K] -> CA int8 [M, K_pad] (outlier columns of the row's segment zeroed), SCA [M] and the
 //                       compacted outlier activations XO fp16 [M, count] (zero where the column is not the row's segment's)
 //   i8_lora_down        T fp32 [M, R] = X . A^T (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 sums)
-//   i8_gemm             y = acc * SCA * SCB / 127^2 + XO . (CB * SCB / 127)[cols]^T + scaling * T . B^T (+ residual)
+//   i8_gemm             y = acc * SCA * SCB / 127^2 (+ bias) + XO . (CB * SCB / 127)[cols]^T + scaling * T . B^T (+ residual)
 //                       main loop v_mfma_i32_32x32x32_i8, int32 accumulation; the LoRA term an fp32 MFMA side loop of the
 //                       epilogue on the same 32 x 32 tiles, the (few) outlier columns one fma each
 #include "common.h"
@@ -195,6 +195,7 @@ struct I8GemmArgs {
     const int* cnt;       // device count
     const float* t;       // LoRA down-projection [m, ldt] or null
     const float* lb;      // LoRA B [n_pad, r] (r % 8 == 0)
+    const float* bias;    // fp32 [n] or null
     const float* res;     // fp32 residual [m, ldr] or null
     void* out;
     int64_t ldr, ldc;
@@ -255,6 +256,7 @@ __global__ __launch_bounds__(256) void i8_gemm(I8GemmArgs p) {
             if (nt >= p.n) continue;
             const int col = nt + (lane & 31);                       // < n_pad
             const float sb = p.scb[col];
+            const float bv = (p.bias && col < p.n) ? p.bias[col] : 0.0f;      // bias has n entries, col runs to n_pad
             float16v side = {}, lora = {};
             if (n_out > 0) {                                         // outlier columns against the dequantised int8 weight: one fma
                 const int8_t* cbr = p.b + (int64_t)col * p.k_pad;    // per column in list order, so a column of another segment
@@ -286,6 +288,7 @@ __global__ __launch_bounds__(256) void i8_gemm(I8GemmArgs p) {
                     continue;
                 }
                 float v = (float)acc[i][j][e] * p.sca[row] * sb / 16129.0f;
+                if (p.bias) v = v + bv;                              // fp32, next to the dequantised accumulator
                 v = v + side[e];
                 v = v + p.scaling * lora[e];
                 if (p.res) v += p.res[row * p.ldr + col];
@@ -364,8 +367,8 @@ int astts_op_i8_lora_down(const void* x_f16, int64_t ldx, const float* a, int32_
 
 int astts_op_i8_gemm(const int8_t* ca, const float* sca, const int8_t* cb, const float* scb, int32_t m, int32_t n, int32_t k_pad,
                      const void* xo_f16, int32_t ldo, const int32_t* cols, const int32_t* cnt, const float* t, int32_t ldt,
-                     const float* lora_b, int32_t r, int32_t g1, int32_t g2, float scaling, const float* residual, int64_t ldr,
-                     void* out, int32_t out_kind, int64_t ldc, astts_stream_t stream) {
+                     const float* lora_b, int32_t r, int32_t g1, int32_t g2, float scaling, const float* bias, const float* residual,
+                     int64_t ldr, void* out, int32_t out_kind, int64_t ldc, astts_stream_t stream) {
     ASTTS_REQUIRE(ca && sca && cb && scb && out, ASTTS_ERR_INVALID, "astts_op_i8_gemm: null pointer");
     ASTTS_REQUIRE(m >= 1 && n >= 1 && k_pad >= kBK && k_pad % kBK == 0 && ldc >= n && out_kind >= 0 && out_kind <= 2 &&
                       (!residual || ldr >= n),
@@ -375,7 +378,7 @@ int astts_op_i8_gemm(const int8_t* ca, const float* sca, const int8_t* cb, const
     ASTTS_REQUIRE(r == 0 || (t && lora_b && r % 8 == 0 && ldt % 4 == 0 && g1 % 32 == 0 && g2 % 32 == 0 && ((uintptr_t)t & 15) == 0 &&
                              ((uintptr_t)lora_b & 15) == 0),
                   ASTTS_ERR_INVALID, "astts_op_i8_gemm: bad LoRA operands (r=%d, ldt=%d, group bounds %d %d)", r, ldt, g1, g2);
-    I8GemmArgs p{ca, sca, cb, scb, (const _Float16*)xo_f16, cols, cnt, t, lora_b, residual, out, ldr, ldc,
+    I8GemmArgs p{ca, sca, cb, scb, (const _Float16*)xo_f16, cols, cnt, t, lora_b, bias, residual, out, ldr, ldc,
                  m, n, k_pad, ldo, ldt, r, g1, g2, out_kind, scaling};
     const int64_t blocks = cdiv(m, kBM) * cdiv(n, kBN);
     ASTTS_REQUIRE(blocks < (1ll << 31), ASTTS_ERR_INVALID, "astts_op_i8_gemm: grid too large");

@@ -501,15 +501,16 @@ int astts_op_i8_quant_act(const void* x_f16, int64_t ldx, const int32_t* seg, in
 int astts_op_i8_lora_down(const void* x_f16, int64_t ldx, const float* a, int32_t m, int32_t k, int32_t r_tot, float* t, int32_t ldt,
                           astts_stream_t stream);
 /* out[m, n] = acc * SCA[m] * SCB[n] / 127^2  (acc = sum_k CA . CB, exact int32, v_mfma_i32_32x32x32_i8)
+ *           + bias[n]                            (fp32 [n], or NULL; an fp32 addition: bitsandbytes adds it in fp16)
  *           + sum_{j < *cnt} xo[m, j] * (CB[n, cols[j]] * SCB[n] / 127)          (xo == NULL: no outlier term)
  *           + scaling * sum_{i < r} t[m, g(n) * r + i] * lora_b[n, i]            (r == 0: no LoRA term; g(n) = (n >= g1) + (n >= g2),
  *                                                                                  g1, g2 multiples of 32: the parts of a fused weight)
- *           + residual[m, n] (fp32, or NULL).  out_kind 0: fp32, 1: fp16, 2: the raw int32 accumulator.  lora_b fp32 [n_pad, r],
- * r % 8 == 0.  CB / SCB as astts_op_i8_quant_weight made them (n_pad >= n rounded up to 128). */
+ *           + residual[m, n] (fp32, or NULL).  out_kind 0: fp32, 1: fp16, 2: the raw int32 accumulator (no term but acc).  lora_b fp32
+ * [n_pad, r], r % 8 == 0.  CB / SCB as astts_op_i8_quant_weight made them (n_pad >= n rounded up to 128). */
 int astts_op_i8_gemm(const int8_t* ca, const float* sca, const int8_t* cb, const float* scb, int32_t m, int32_t n, int32_t k_pad,
                      const void* xo_f16, int32_t ldo, const int32_t* cols, const int32_t* cnt, const float* t, int32_t ldt,
-                     const float* lora_b, int32_t r, int32_t g1, int32_t g2, float scaling, const float* residual, int64_t ldr,
-                     void* out, int32_t out_kind, int64_t ldc, astts_stream_t stream);
+                     const float* lora_b, int32_t r, int32_t g1, int32_t g2, float scaling, const float* bias, const float* residual,
+                     int64_t ldr, void* out, int32_t out_kind, int64_t ldc, astts_stream_t stream);
 
 /* LayerNorm (scale / shift folded into the weights by the caller) + q|k|v projection + masked multi-head attention of one
  * transformer block of the flow estimator in one launch (csrc/ops_tfm_fused.hip): x fp32 [b, t, c] -> out fp16
