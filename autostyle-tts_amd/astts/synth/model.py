@@ -350,6 +350,10 @@ class AcousticLM:
                       key_start: Optional[torch.Tensor] = None):
         return self.decode_prefilled(self.prefill(prefix, n_steps, key_start), uniforms, ignore_eos, forced_tokens, return_logits)
 
+    def session(self, rows_max: int, t_arena: int, stream=None) -> "LmSession":
+        """A decode chain that a second batch can join while the first is decoding (LmSession)."""
+        return LmSession(self, rows_max, t_arena, stream)
+
     WIDE_ROWS = 256      # ASTTS_LM_MAX_ROWS: rows of one wide-engine call
 
     def decode(self, prefix: torch.Tensor, n_steps: int, uniforms: torch.Tensor, ignore_eos: bool = True,
@@ -439,6 +443,113 @@ class AcousticLM:
         if return_logits:
             return toks, torch.stack(all_logits, dim=1)
         return toks
+
+
+class LmSession:
+    """One decode chain of the C++ engine that up to two prefilled batches share (include/session/astts_lm_session.h): a batch
+    admitted while another is decoding JOINS it, and the chain's launches (72 per token, each a latency link) carry the rows of both.
+    Every row's tokens and logits are bit-identical to ``AcousticLM.decode_prefilled`` of its batch alone (tested).
+
+    ``rows_max`` <= 32 rows in all; ``t_arena`` >= twice the longest window (prefix + steps - 1) that will be admitted.  The session
+    allocates layers * t_arena * rows_max * 4 d bytes of cache arena (0.94 GB at CosyVoice-300M widths, 1024 positions, 16 rows).
+    All calls enqueue on ``stream`` (the stream current at construction by default) and none waits for the GPU; they are not
+    thread-safe: one thread drives a session."""
+
+    def __init__(self, lm: "AcousticLM", rows_max: int, t_arena: int, stream=None):
+        import ctypes
+
+        from .. import _lib, _lib_session
+        self.lm, self.rows_max, self.t_arena = lm, int(rows_max), int(t_arena)
+        self.stream = stream if stream is not None else torch.cuda.current_stream(lm.device)
+        self._lib = _lib_session.load()
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.astts_lm_session_create(lm._engine(), self.rows_max, self.t_arena, _lib.stream_ptr(self.stream), ctypes.byref(h)))
+        self._h = h
+        self._ctx = [None, None]          # per slot: the buffers of the batch that holds it (read by kernels until its last step)
+
+    def close(self) -> None:
+        from .. import _lib
+        if self._h is not None:
+            h, self._h = self._h, None
+            _lib.check(self._lib.astts_lm_session_destroy(h))
+
+    def __del__(self):
+        import sys
+        if sys is None or sys.is_finalizing():      # at interpreter exit the process gives the memory back
+            return
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001
+            pass
+
+    @property
+    def max_window(self) -> int:
+        return self.t_arena // 2
+
+    def active(self) -> int:
+        return sum(c is not None for c in self._ctx)
+
+    def steps_left(self) -> List[int]:
+        """Steps still to be enqueued, per admitted batch."""
+        return [c["n_steps"] - c["next"] for c in self._ctx if c is not None]
+
+    def can_admit(self, b: int, s0: int, n_steps: int) -> bool:
+        return int(self._lib.astts_lm_session_can_admit(self._h, int(b), int(s0), int(n_steps))) >= 0
+
+    def admit(self, state, uniforms: torch.Tensor, ignore_eos=True, forced_tokens: Optional[torch.Tensor] = None,
+              return_logits: bool = False):
+        """``state``: what ``AcousticLM.prefill`` returned.  -> the batch's context: ``ctx["toks"]`` (and ``ctx["logits"]``) are complete
+        once ``step`` has returned it.  The prefill's cache is copied into the session's arena (stream order)."""
+        import ctypes
+
+        from .. import _lib
+        lm = self.lm
+        b, n_steps, s0, cache, key_start = (state[k] for k in ("b", "n_steps", "s0", "cache", "key_start"))
+        ctx = dict(state)
+        with torch.cuda.stream(self.stream):
+            ctx.update({"toks": torch.zeros((b, n_steps), dtype=torch.int32, device=lm.device),
+                        "logits": torch.empty((b, n_steps, lm.cfg.speech_vocab + 1), dtype=torch.float32, device=lm.device) if return_logits else None,
+                        "forced": None if forced_tokens is None else forced_tokens.to(torch.int32).contiguous(),
+                        "u": uniforms.to(torch.float32).contiguous(), "ignore_eos": ignore_eos, "next": 0})
+            ptrs = (ctypes.c_void_p * len(cache))(*[c.data_ptr() for c in cache])
+            slot = ctypes.c_int32(-1)
+            _lib.check(self._lib.astts_lm_session_admit(
+                self._h, ctx["logits0"].data_ptr(), ptrs, None if key_start is None else key_start.data_ptr(), s0 + n_steps, b, s0, n_steps,
+                ctx["u"].data_ptr(), None if ctx["forced"] is None else ctx["forced"].data_ptr(), lm._eos_min(ignore_eos, n_steps),
+                ignore_eos.data_ptr() if torch.is_tensor(ignore_eos) else None, ctx["toks"].data_ptr(),
+                None if ctx["logits"] is None else ctx["logits"].data_ptr(), ctypes.byref(slot)))
+        # the prefill's cache and first logits are read by the admission on this session's stream only: tell the allocator, then let go
+        for t in lm.prefill_tensors(state):
+            t.record_stream(self.stream)
+        ctx.pop("cache")
+        ctx.pop("logits0")
+        ctx["slot"] = int(slot.value)
+        self._ctx[ctx["slot"]] = ctx
+        return ctx
+
+    def step(self, k: int):
+        """Enqueue up to ``k`` token steps of every admitted batch as one chain.  -> the contexts of the batches that ended."""
+        import ctypes
+
+        from .. import _lib
+        mask = ctypes.c_uint32(0)
+        live = [c for c in self._ctx if c is not None]
+        k = int(k)
+        with torch.cuda.stream(self.stream):
+            _lib.check(self._lib.astts_lm_session_step(self._h, k, ctypes.byref(mask)))
+        done = []
+        for c in live:
+            c["next"] = min(c["n_steps"], c["next"] + k)
+        for slot in (0, 1):
+            if mask.value >> slot & 1:
+                done.append(self._ctx[slot])
+                self._ctx[slot] = None
+        return done
+
+    def run(self) -> None:
+        """Enqueue every remaining step of the admitted batches."""
+        while self.active():
+            self.step(max(self.steps_left()))
 
 
 class _Resnet1D:
@@ -964,6 +1075,157 @@ def _lib_check_spin(us: int, stream) -> None:
     _lib.check(_lib.load().astts_stream_spin(int(us), int(stream.cuda_stream)))
 
 
+class _JoinChain:
+    """One decode chain of ``PipelinedSynth(join=True)``: a stream, an LmSession on it and the host thread that drives it -- admit
+    what is waiting, enqueue a range of steps, hand over every batch that ended, stay a bounded number of ranges ahead of the GPU.
+
+    The session's arena is sized by the SUBMITTING thread, under the chain's lock (``reserve``): the longest window it has accepted,
+    rounded up to 128 positions and never past the position tables.  A longer batch is accepted only while the chain holds no batch
+    (its session is then replaced by a larger one before the batch is admitted); otherwise the chain answers "not now"."""
+
+    ROWS_MAX = 16            # two batches of up to 8 rows side by side (a wider arena spreads a row's keys further apart: lm_step.h)
+
+    def __init__(self, pipe: "PipelinedSynth", index: int):
+        import threading
+        from collections import deque
+
+        self.pipe, self.index, self.stream = pipe, index, pipe.s_lm[index]
+        self.session = None                 # created / replaced by the chain's thread only, at the size `_half` asks for
+        self._cv = threading.Condition()
+        self._waiting = deque()             # (state, uniforms, event, future) of batches not admitted yet
+        self._occupied = 0                  # batches accepted and not handed over
+        self._half = 0                      # longest window the chain has promised to take (arena = 2 * _half positions)
+        self._stop = False
+        self._dead = None                   # the exception that ended the chain's thread
+        self._thread = None
+        self.gate = threading.Event()       # cleared: the thread admits nothing and enqueues nothing (tests: queue two batches, then open)
+        self.gate.set()
+        self.joins = 0                      # batches admitted while another was decoding on this chain
+
+    def occupied(self) -> int:
+        with self._cv:
+            return self._occupied
+
+    def reserve(self, window: int) -> bool:
+        """Take a slot for a batch with this window (prefix + steps - 1 keys) if the chain can hold it now.  Called by the submitting
+        thread; on True the batch must be handed to ``submit``."""
+        with self._cv:
+            if self._dead is not None:
+                raise RuntimeError(f"decode chain {self.index} stopped: {self._dead!r}") from self._dead
+            if self._occupied >= 2 or window > self.pipe.eng.lm.body.center:
+                return False
+            if window > self._half:
+                if self._occupied:
+                    return False            # a running batch lives in the smaller arena
+                self._half = min((window + 127) // 128 * 128, self.pipe.eng.lm.body.center)
+            self._occupied += 1
+            return True
+
+    def submit(self, state, lm_args):
+        import threading
+        from concurrent.futures import Future
+
+        cur = torch.cuda.current_stream(self.pipe.eng.device)
+        for t in lm_args:                   # read on the chain's stream for the whole decode (see PipelinedSynth._launch_group)
+            if isinstance(t, torch.Tensor):
+                t.record_stream(self.stream)
+        for t in self.pipe.eng.lm.prefill_tensors(state):
+            t.record_stream(self.stream)
+        ready = torch.cuda.Event()
+        ready.record(cur)                   # the prefill (and whatever built the inputs) on the caller's stream
+        fut = Future()
+        with self._cv:
+            if self._dead is not None:
+                self._occupied -= 1
+                raise RuntimeError(f"decode chain {self.index} stopped: {self._dead!r}") from self._dead
+            self._waiting.append((state, lm_args[5], ready, fut))
+            if self._thread is None:
+                self._thread = threading.Thread(target=self._run, name=f"astts-join-chain-{self.index}", daemon=True)
+                self._thread.start()
+            self._cv.notify()
+        return fut
+
+    def close(self) -> None:
+        with self._cv:
+            self._stop = True
+            self._cv.notify()
+        self.gate.set()
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+        if self.session is not None:
+            self.session.close()
+            self.session = None
+
+    def _admit_waiting(self, futs) -> None:
+        lm = self.pipe.eng.lm
+        while True:
+            with self._cv:
+                if not self._waiting:
+                    return
+                state, u, ready, fut = self._waiting[0]
+                half = self._half
+            idle = self.session is None or not self.session.active()
+            if idle and (self.session is None or self.session.max_window < half):
+                if self.session is not None:          # the chain has promised a longer window than its arena holds: a larger one
+                    self.session.close()
+                    self.session = None
+                self.session = lm.session(self.ROWS_MAX, 2 * half, self.stream)
+            if not self.session.can_admit(state["b"], state["s0"], state["n_steps"]):
+                if not idle:
+                    return                            # no free rows beside the running batch: it goes in when that one has ended
+                with self._cv:                        # an idle session that cannot take it never will: this batch fails, the chain goes on
+                    self._waiting.popleft()
+                    self._occupied -= 1
+                fut.set_exception(RuntimeError(f"decode chain {self.index}: a batch of {state['b']} rows with a window of "
+                                               f"{state['s0'] + state['n_steps'] - 1} keys does not fit a session of {self.ROWS_MAX} rows "
+                                               f"and {self.session.max_window} keys"))
+                continue
+            self.joins += 0 if idle else 1
+            self.stream.wait_event(ready)
+            futs[id(self.session.admit(state, u, ignore_eos=True))] = fut
+            with self._cv:
+                self._waiting.popleft()
+
+    def _run(self):
+        from collections import deque
+
+        pipe = self.pipe
+        ahead = deque()
+        futs = {}
+        try:
+            with torch.cuda.device(pipe.eng.device), torch.cuda.stream(self.stream):
+                while True:
+                    self.gate.wait()
+                    with self._cv:
+                        while not self._stop and not self._waiting and not (self.session is not None and self.session.active()):
+                            self._cv.wait()
+                        if self._stop:
+                            return
+                    self._admit_waiting(futs)
+                    if not self.session.active():
+                        continue
+                    done = self.session.step(min(pipe.JOIN_QUANTUM, min(self.session.steps_left())))
+                    mark = torch.cuda.Event()
+                    mark.record(self.stream)
+                    for ctx in done:
+                        with self._cv:
+                            self._occupied -= 1
+                        futs.pop(id(ctx)).set_result(([ctx["toks"]], mark))
+                    ahead.append(mark)
+                    if len(ahead) > pipe.JOIN_AHEAD:
+                        ahead.popleft().synchronize()
+        except BaseException as e:      # noqa: BLE001  (handed to whoever waits for a batch of this chain; later submits raise)
+            with self._cv:
+                self._dead = e
+                pending = [w[3] for w in self._waiting]
+                self._waiting.clear()
+                self._occupied = 0
+            for f in list(futs.values()) + pending:
+                if not f.done():
+                    f.set_exception(e)
+
+
 class PipelinedSynth:
     """Software pipeline over consecutive (independent) batches on several HIP streams of one GPU.
 
@@ -979,11 +1241,25 @@ class PipelinedSynth:
     together) run as ONE decode chain with their rows side by side -- the chain's ~19k launches are latency-bound and cost
     about the same for 16 rows as for 8 -- and each batch is then rendered on its own.  Rows are independent in every LM
     kernel (GEMM rows, per-(row, head) attention, per-row sampler with per-row uniforms), so every batch's tokens, mel and
-    waveform are bit-identical to running it alone (tested)."""
+    waveform are bit-identical to running it alone (tested).
+
+    ``join``: each of the ``lm_depth`` chains is a decode SESSION (LmSession) with two slots and a host thread of its own.  A submitted
+    batch joins a chain that is already decoding -- its launches then carry the rows of both batches -- or starts an idle one; no batch
+    waits for a partner.  Only when all ``2 * lm_depth`` slots are taken does ``submit`` render the oldest batch first, as it does
+    without ``join`` when every chain is busy.  Same bits as running each batch alone (tested).  Batches a session cannot take (more
+    than 8 rows, the wide engine, windows past the position tables) get a chain call of their own as without ``join``; batches
+    need not have equal prefix or decode lengths.
+    Footprint: every chain keeps a daemon host thread and its session's cache arena -- layers * 2 * window * 16 rows * 4 d bytes,
+    0.94 GB per chain at CosyVoice-300M widths and windows of up to 512 keys, 2.8 GB at three chains -- until ``close()`` is called
+    (``autotune`` closes the pipelines it does not return; the one it returns is the caller's to close).  A chain whose arena is too
+    short for a batch is given a longer one when it holds no batch."""
+
+    JOIN_QUANTUM = 16        # token steps a chain's thread enqueues between two looks at its queue of batches that want to join
+    JOIN_AHEAD = 2           # ... and the ranges it keeps enqueued ahead of the GPU: a batch can only join what is not enqueued yet
 
     def __init__(self, engine: "SynthEngine", lm_depth: int = 2, lm_priority: int = -1, render_priority: int = 0, streams=None,
                  cobatch: int = 1, render_depth: int = 1, pipe_classes=None, front_prefill: Optional[bool] = None,
-                 stagger_ms: Optional[float] = None, wide_lm: bool = False):
+                 stagger_ms: Optional[float] = None, wide_lm: bool = False, join: bool = False):
         import os
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
@@ -1046,6 +1322,15 @@ class PipelinedSynth:
         self.stagger_ms = float(os.environ.get("ASTTS_PIPE_STAGGER_MS", "0")) if stagger_ms is None else float(stagger_ms)
         self._staggered = set()
         self._i = 0
+        self.join = bool(join) and self.cobatch == 1 and not self.wide_lm
+        self._chains = [_JoinChain(self, c) for c in range(self.depth)] if self.join else []
+
+    def close(self) -> None:
+        """Stop the chains' threads and free their sessions (``join``); the pipeline must be drained."""
+        for ch in self._chains:
+            ch.close()
+        self._chains = []
+        self._pool.shutdown(wait=True)
 
     @classmethod
     def autotune(cls, engine: "SynthEngine", sample_args, depths=(3, 2), trials: int = 3, steps: int = 4, verbose: bool = False,
@@ -1066,13 +1351,21 @@ class PipelinedSynth:
         per_cfg = []                        # (best pipe, best time) per configuration, in the order of `depths`
         with torch.cuda.device(engine.device):
             classes = ops.stream_pipe_classes(device=engine.device, verbose=verbose)      # one probe for all trials
+        # every depth both ways: separate chains, and chains that a second batch joins (``join``)
+        tried = []
         for cfg_ in depths:
             cfg_ = cfg_ if isinstance(cfg_, tuple) else (cfg_, 1)
-            depth, cob, rdep = (tuple(cfg_) + (1,))[:3]
+            for join in (False, True):
+                if join and (cfg_[1] != 1 or wide_lm):
+                    continue
+                tried.append(tuple(cfg_) + ("join",) if join else cfg_)
+        for cfg_ in tried:
+            join = cfg_[-1] == "join"
+            depth, cob, rdep = (tuple(cfg_[:-1] if join else cfg_) + (1,))[:3]
             for _ in range(trials):
                 lm_prio = int(os.environ.get("ASTTS_PIPE_LM_PRIORITY", "0"))      # experiments: -1 = high-priority decode streams
                 pipe = cls(engine, lm_depth=depth, lm_priority=lm_prio, render_priority=0, cobatch=cob, render_depth=rdep,
-                           pipe_classes=classes if rdep == 1 and lm_prio == 0 else None, wide_lm=wide_lm)
+                           pipe_classes=classes if rdep == 1 and lm_prio == 0 else None, wide_lm=wide_lm, join=join)
                 with torch.cuda.stream(pipe.front_stream):
                     for _ in range((depth + 1) * cob):
                         if front is not None:
@@ -1089,19 +1382,26 @@ class PipelinedSynth:
                     torch.cuda.synchronize(engine.device)
                 dt = (time.perf_counter() - t0) / steps
                 if verbose:
-                    print(f"PipelinedSynth.autotune: depth {depth} cobatch {cob} render streams {rdep}: {dt * 1e3:.1f} ms/batch", flush=True)
+                    print(f"PipelinedSynth.autotune: depth {depth} cobatch {cob} render streams {rdep} join {join}: {dt * 1e3:.1f} ms/batch", flush=True)
                 if dt < best_dt:
                     best, best_dt = pipe, dt
                 if not per_cfg or per_cfg[-1][2] != cfg_:
                     per_cfg.append([pipe, dt, cfg_])
                 elif dt < per_cfg[-1][1]:
+                    if per_cfg[-1][0] is not best:
+                        per_cfg[-1][0].close()
                     per_cfg[-1][0], per_cfg[-1][1] = pipe, dt
+                else:
+                    pipe.close()
         if dist is not None and len(per_cfg) > 1:
             t = torch.tensor([c[1] for c in per_cfg], dtype=torch.float64, device=engine.device)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             k = int(torch.argmin(t).item())
             best, best_dt = per_cfg[k][0], per_cfg[k][1]
             best.tuned_agreed_over_ranks = True
+        for c in per_cfg:                   # the chains' threads and sessions of every configuration that lost
+            if c[0] is not best:
+                c[0].close()
         best.tuned_ms_per_batch = best_dt * 1e3
         best.tuned_table_ms = {str(c[2]): round(c[1] * 1e3, 2) for c in per_cfg}
         return best
@@ -1187,6 +1487,8 @@ class PipelinedSynth:
             sr.wait_stream(cur)
         item = {"lm": (text, text_lens, lm_spk, lm_prompt_tokens, n_tokens, uniforms),
                 "render": (flow_prompt_tokens, flow_prompt_mel, flow_spk, z, phase0, noise), "fut": None, "k": 0}
+        if self.join and self._join_submit(item):
+            return self._render(self._fifo.popleft()) if len(self._fifo) > 2 * self.depth else None
         if self._pending and not self._compatible(self._pending[0]["lm"], item["lm"]):
             self._launch_group()
         self._pending.append(item)
@@ -1197,6 +1499,38 @@ class PipelinedSynth:
         if len(self._fifo) > self.depth * self.cobatch and self._fifo[0]["fut"] is not None:
             return self._render(self._fifo.popleft())
         return None
+
+    def _join_submit(self, item) -> bool:
+        """``join``: prefix and prefill on the caller's stream, then the batch goes to a chain that can hold it -- one that is already
+        decoding if there is one (that is the join), else an idle one.  While no chain can (every slot taken, or a window longer than
+        the arenas of the chains that are busy) the batches before it are waited for, oldest first: a chain hands a batch over when its
+        last step is enqueued, and a chain without batches takes any window the position tables allow.
+        -> False: not a batch a session takes (nothing is enqueued then)."""
+        lm, lm_args = self.eng.lm, item["lm"]
+        text, text_lens, lm_spk, lm_prompt_tokens, n_tokens = lm_args[:5]
+        if int(text.shape[0]) > _JoinChain.ROWS_MAX // 2:
+            return False
+        pre = lm.prefix(text, text_lens, lm_spk, lm_prompt_tokens)
+        window = int(pre.shape[0]) + int(n_tokens) - 1
+        if window > lm.body.center:
+            return False
+        state = lm.prefill(pre, n_tokens)
+        order = lambda: sorted(self._chains, key=lambda ch: (ch.occupied() != 1, ch.index))     # noqa: E731
+        chain = next((ch for ch in order() if ch.reserve(window)), None)
+        for older in list(self._fifo):
+            if chain is not None:
+                break
+            if older["fut"] is not None:
+                try:
+                    older["fut"].result()
+                except Exception:      # noqa: BLE001  (raised again where that batch is rendered)
+                    pass
+                chain = next((ch for ch in order() if ch.reserve(window)), None)
+        if chain is None:
+            raise RuntimeError("PipelinedSynth: no decode chain can take the batch although none holds one")
+        self._fifo.append(item)
+        item["fut"] = chain.submit(state, lm_args)
+        return True
 
     def _compatible(self, a, b) -> bool:
         """Batches can share a decode chain when their prefix and decode lengths agree (fixed-length batches of one job)."""

@@ -12,7 +12,11 @@
 //   step_wide  33 .. ASTTS_LM_MAX_ROWS rows, plain GEMMs over all rows (7 per layer)
 // The workspace has two layouts, each written ONCE as a carve function that counts the bytes (astts_lm_workspace_bytes) and hands out
 // the pointers (astts_lm_decode): carve_narrow, shared by v1 and v2, and carve_wide.
+// A decode SESSION (astts_lm_session_*, include/session/astts_lm_session.h) is the same loop and step_v2 over a WINDOW of rows of a
+// cache arena that up to two batches share: a batch admitted while another is decoding joins its chain (bookkeeping: lm_session.h).
 #include "common.h"
+#include "lm_session.h"
+#include "../../include/session/astts_lm_session.h"
 #include "lm_step.h"
 
 #include <cstdlib>
@@ -35,18 +39,28 @@ using namespace astts;
 
 namespace {
 
-// what astts_lm_decode received (include/astts.h), after validation
-struct DecodeCall {
-    const float* logits0;
-    void* const* kv_cache;
-    const int32_t* key_start;
-    int32_t t_max, b, pos0, n_steps, s_begin, s_end;
+// the rows of one decode inside a call: what the sampler and the logits copy need.  astts_lm_decode has one group, all rows of the call;
+// a session step (astts_lm_session_step) has one or two, each at its own step index
+struct RowGroup {
+    int32_t row0, b;             // rows [row0, row0 + b) of the call
+    int32_t n_steps, s_off;      // steps of its decode; its step index is the loop's s + s_off
     const float* uniforms;
     const int32_t* forced_tokens;
     int32_t eos_min_steps;
     const int32_t* eos_min_rows;
     int32_t* tokens_out;
     float* logits_out;
+};
+
+// what astts_lm_decode received (include/astts.h), after validation -- or one range of steps of a session
+struct DecodeCall {
+    const float* logits0;
+    void* const* kv_cache;
+    const int32_t* key_start;
+    int32_t t_max, b, pos0, s_begin, s_end;
+    int32_t kv_rows;             // rows of the time-major cache the pointers lead into (== b unless the call is a row window of a session's arena)
+    RowGroup g[2];
+    int32_t n_groups;
     hipStream_t st;
 };
 
@@ -124,18 +138,27 @@ size_t carve_wide(const astts_lm* h, int b, char* base, WideWs* W) {
 // logits the previous range left in the workspace (`lg`: the caller passes the SAME workspace, token buffer and cache to every range of
 // one decode).  advance(pos) issues the forward pass of the tokens in `tok` at position pos and leaves the next logits in `lg`; the last
 // step of a decode only samples.  (A template parameter, not a function pointer: the step is launch-rate bound.)
+// With two groups (a session) the sampler serves both in ONE launch, and advance() runs while any group has a step left: it is the
+// session's advance that narrows the rows to the groups that go on (astts_lm_session_step).
 template <class Advance>
 int run_steps(const astts_lm_config_t& c, const DecodeCall& k, float* lg, int32_t* tok, Advance advance) {
     const float* cur = k.s_begin == 0 ? k.logits0 : lg;
     for (int s = k.s_begin; s < k.s_end; ++s) {
-        if (k.logits_out)
-            ASTTS_CHECK_HIP(hipMemcpy2DAsync(k.logits_out + (size_t)s * c.vocab_out, sizeof(float) * (size_t)k.n_steps * c.vocab_out,
-                                             cur, sizeof(float) * c.vocab_out, sizeof(float) * c.vocab_out, k.b,
-                                             hipMemcpyDeviceToDevice, k.st));
-        RUN(astts_op_ras_sample_ex(cur, k.tokens_out, k.uniforms + (size_t)s * k.b * 2, tok, k.b, c.vocab_out, s, k.n_steps, c.top_k,
-                                   c.top_p, c.ras_win, c.ras_tau, c.speech_vocab, (s < k.eos_min_steps ? 1 : 0) | (c.eos_policy ? 2 : 0),
-                                   k.eos_min_rows, k.forced_tokens, k.st));
-        if (s + 1 == k.n_steps) break;
+        SampleGroup sg[2];
+        bool last = true;
+        for (int i = 0; i < k.n_groups; ++i) {
+            const RowGroup& r = k.g[i];
+            const int sr = s + r.s_off;
+            if (r.logits_out)
+                ASTTS_CHECK_HIP(hipMemcpy2DAsync(r.logits_out + (size_t)sr * c.vocab_out, sizeof(float) * (size_t)r.n_steps * c.vocab_out,
+                                                 cur + (size_t)r.row0 * c.vocab_out, sizeof(float) * c.vocab_out, sizeof(float) * c.vocab_out,
+                                                 r.b, hipMemcpyDeviceToDevice, k.st));
+            sg[i] = SampleGroup{r.tokens_out, r.uniforms + (size_t)sr * r.b * 2, r.forced_tokens, r.eos_min_rows, r.b, r.row0, sr, r.n_steps,
+                                sr < r.eos_min_steps ? 1 : 0};
+            last = last && sr + 1 == r.n_steps;
+        }
+        RUN(ras_sample_groups_launch(cur, tok, c.vocab_out, c.top_k, c.top_p, c.ras_win, c.ras_tau, c.speech_vocab, c.eos_policy, sg, k.n_groups, k.st));
+        if (last) break;
         RUN(advance(k.pos0 + s));
         cur = lg;
     }
@@ -165,7 +188,7 @@ int step_v2(const astts_lm* h, const DecodeCall& k, const NarrowWs::V2& w, int p
     // ASTTS_LM_FFN_SPLIT=0: FFN-out as one workgroup per column block over the whole K (rounds 2-3)
     static const bool ffn_split_env = exp_env_int("ASTTS_LM_FFN_SPLIT", 1) != 0;
     const bool ffn_split = ffn_split_env && (c.ffn & 255) == 0;
-    const KvLayout lay = KvLayout::time_major(b, d);
+    const KvLayout lay = KvLayout::time_major(k.kv_rows, d);
     auto gemv = [&]() {
         GemvArgs a;
         memset(&a, 0, sizeof(a));
@@ -334,7 +357,52 @@ int step_wide(const astts_lm* h, const DecodeCall& k, const WideWs& w, int pos) 
     return gemm_ln(x, g.after_g, g.after_b, g.head_w, g.head_b, w.lg, 0, c.vocab_out, c.vocab_out, ASTTS_ACT_NONE, nullptr, 0, 0);
 }
 
+
+// ---- decode session (include/session/astts_lm_session.h): ONE chain that up to two batches share.  The bookkeeping -- rows, arena
+// positions, how many steps fit one range, when to rebase -- is lm_session.h (no HIP); here are the two copy kernels and the calls.
+constexpr int kSessionMaxLayers = 32;
+struct KvPtrs { _Float16* p[kSessionMaxLayers]; };
+
+// Admission: the valid prefix keys [key_start[r], pos0) of every layer move from the prefill's cache [t][rows][2d] to the arena
+// [t + shift][arena rows][2d] (dst leads to the group's first row), 16 bytes per thread and iteration; block (0, 0) writes the rows'
+// shifted key_start.  grid (pos0, layers).
+__global__ __launch_bounds__(256) void lm_kv_admit(KvPtrs src, KvPtrs dst, const int* kstart_src, int* kstart_dst, int rows, int shift,
+                                                   int64_t src_t, int64_t dst_t, int row_vec) {
+    const int t = blockIdx.x, tid = threadIdx.x;
+    const uint4* sp = reinterpret_cast<const uint4*>(src.p[blockIdx.y] + (int64_t)t * src_t);
+    uint4* dp = reinterpret_cast<uint4*>(dst.p[blockIdx.y] + (int64_t)(t + shift) * dst_t);
+    for (int i = tid; i < rows * row_vec; i += 256) {
+        const int r = i / row_vec;
+        if (kstart_src && t < kstart_src[r]) continue;
+        dp[i] = sp[i];
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < rows) kstart_dst[tid] = (kstart_src ? kstart_src[tid] : 0) + shift;
+}
+
+// Rebase: arena positions [src0, src0 + gridDim.x) of rows [0, rows) (kv leads to the first of them) move down by delta -- source and
+// destination do not overlap (SessionPlan::rebase) -- and the rows' key_start (kstart leads to the first of them) drops by the same
+// amount.  grid (n, layers).
+__global__ __launch_bounds__(256) void lm_kv_rebase(KvPtrs kv, int* kstart, int rows, int src0, int delta, int64_t t_stride, int row_vec) {
+    const int t = src0 + blockIdx.x, tid = threadIdx.x;
+    const uint4* sp = reinterpret_cast<const uint4*>(kv.p[blockIdx.y] + (int64_t)t * t_stride);
+    uint4* dp = reinterpret_cast<uint4*>(kv.p[blockIdx.y] + (int64_t)(t - delta) * t_stride);
+    for (int i = tid; i < rows * row_vec; i += 256) dp[i] = sp[i];
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < rows) kstart[tid] -= delta;
+}
+
 }  // namespace
+
+struct astts_lm_session {
+    astts_lm* h;
+    hipStream_t st;
+    SessionPlan plan;
+    char* mem;                 // one allocation: arenas, workspace, key_start
+    KvPtrs arena;              // [t_arena][rows_max][2d] fp16 per layer
+    NarrowWs ws;               // for rows_max rows
+    int32_t* kstart;           // [rows_max] first valid key of every row, in arena positions
+    RowGroup rows[SessionPlan::kGroups];   // what each admitted group's sampler needs (row0 / s_off are set per range)
+    int64_t rebases;
+};
 
 extern "C" {
 
@@ -377,8 +445,8 @@ int astts_lm_decode(astts_lm_t* h, const float* logits0, void* const* kv_cache, 
                   "astts_lm_decode: pos0=%d n_steps=%d t_max=%d", pos0, n_steps, t_max);
     ASTTS_REQUIRE(workspace_bytes >= astts_lm_workspace_bytes(h, b) && ((uintptr_t)workspace & 255) == 0,
                   ASTTS_ERR_WORKSPACE, "astts_lm_decode: workspace too small or misaligned");
-    const DecodeCall k = {logits0, kv_cache, key_start, t_max, b, pos0, n_steps, s_begin, s_end, uniforms, forced_tokens,
-                          eos_min_steps, eos_min_rows, tokens_out, logits_out, (hipStream_t)stream};
+    const DecodeCall k = {logits0, kv_cache, key_start, t_max, b, pos0, s_begin, s_end, b,
+                          {{0, b, n_steps, 0, uniforms, forced_tokens, eos_min_steps, eos_min_rows, tokens_out, logits_out}, {}}, 1, (hipStream_t)stream};
     const astts_lm_config_t& c = h->cfg;
     const bool f16_64 = c.kv_f16 && c.pos_f16 && (c.d % 64) == 0 && (c.ffn % 64) == 0;
     if (b > 32) {
@@ -402,6 +470,175 @@ int astts_lm_decode(astts_lm_t* h, const float* logits0, void* const* kv_cache, 
     }
     ASTTS_CHECK_HIP(hipMemsetAsync(w.skw, 0, 1024, k.st));      // arrival counters start at zero (once per call; they reset themselves)
     return run_steps(c, k, w.lg, w.tok, [&](int pos) { return step_v1(h, k, w, pos); });
+}
+
+// ---- decode session
+namespace {
+
+static size_t session_carve(const astts_lm* h, int rows_max, int t_arena, char* base, astts_lm_session* S) {
+    Carver c{base};
+    for (int l = 0; l < h->cfg.layers; ++l) {
+        _Float16* p = c.take<_Float16>((size_t)t_arena * rows_max * 2 * h->cfg.d);
+        if (S) S->arena.p[l] = p;
+    }
+    int32_t* ks = c.take<int32_t>(rows_max);
+    if (S) S->kstart = ks;
+    const size_t o = align_up(c.o, 256);
+    return o + carve_narrow(h, rows_max, base ? base + o : nullptr, S ? &S->ws : nullptr);
+}
+
+// the launch set of rows [r0, r0 + rows) of a session: a DecodeCall whose pointers lead to row r0 of the arena, of key_start and of the workspace
+struct RowWindow {
+    DecodeCall k;
+    NarrowWs::V2 v;
+    void* kv[kSessionMaxLayers];
+    RowWindow(const astts_lm_session* S, int r0, int rows) {
+        const astts_lm_config_t& c = S->h->cfg;
+        memset(&k, 0, sizeof(k));
+        for (int l = 0; l < c.layers; ++l) kv[l] = S->arena.p[l] + (size_t)r0 * 2 * c.d;
+        v = S->ws.v2(S->plan.rows_max, c.heads);
+        v.h1 += (size_t)r0 * c.d; v.xa += (size_t)r0 * c.d; v.xb += (size_t)r0 * c.d; v.q += (size_t)r0 * c.d;
+        v.ff += (size_t)r0 * c.ffn; v.part_o += (size_t)r0 * c.heads * 2 * 64; v.part_ml += (size_t)r0 * c.heads * 2 * 2;
+        v.lg += (size_t)r0 * c.vocab_out; v.tok += r0;
+        k.logits0 = v.lg; k.kv_cache = kv; k.key_start = S->kstart + r0; k.t_max = S->plan.t_arena; k.b = rows;
+        k.kv_rows = S->plan.rows_max; k.st = S->st;
+    }
+    RowWindow(const RowWindow&) = delete;
+};
+
+}  // namespace
+
+size_t astts_lm_session_bytes(const astts_lm_t* h, int32_t rows_max, int32_t t_arena) {
+    if (!h || rows_max < 1 || rows_max > 32 || t_arena < 4) return 0;
+    return session_carve(h, rows_max, t_arena, nullptr, nullptr);
+}
+
+int astts_lm_session_create(astts_lm_t* h, int32_t rows_max, int32_t t_arena, astts_stream_t stream, astts_lm_session_t** out) {
+    ASTTS_REQUIRE(h && out, ASTTS_ERR_INVALID, "astts_lm_session_create: null argument");
+    const astts_lm_config_t& c = h->cfg;
+    ASTTS_REQUIRE(c.kv_f16 && c.pos_f16 && (c.d % 64) == 0 && (c.ffn % 64) == 0 && c.d <= 1024 && c.layers <= kSessionMaxLayers, ASTTS_ERR_UNSUPPORTED,
+                  "astts_lm_session_create: a session runs the decode-step kernels only (fp16 cache and position tables, d <= 1024, <= %d layers)",
+                  kSessionMaxLayers);
+    SessionPlan plan;
+    ASTTS_REQUIRE(plan.init(rows_max, t_arena) == SESSION_OK, ASTTS_ERR_INVALID, "astts_lm_session_create: rows_max=%d (1..32) t_arena=%d", rows_max, t_arena);
+    ASTTS_REQUIRE(plan.half() <= c.pos_center, ASTTS_ERR_RANGE, "astts_lm_session_create: windows of t_arena / 2 = %d keys pass the position table (%d)",
+                  plan.half(), c.pos_center);
+    ASTTS_REQUIRE(NarrowWs::v2_partial_bytes(rows_max, c.heads) <= astts_op_gemm_fused_workspace_bytes(), ASTTS_ERR_WORKSPACE,
+                  "astts_lm_session_create: the split-key partials of %d rows x %d heads do not fit the split-K area", rows_max, c.heads);
+    astts_lm_session* S = new astts_lm_session();
+    S->h = h; S->st = (hipStream_t)stream; S->plan = plan; S->rebases = 0;
+    const size_t bytes = session_carve(h, rows_max, t_arena, nullptr, nullptr);
+    if (hipMalloc((void**)&S->mem, bytes) != hipSuccess) {
+        delete S;
+        set_error("astts_lm_session_create: hipMalloc of %zu bytes failed", bytes);
+        return ASTTS_ERR_HIP;
+    }
+    session_carve(h, rows_max, t_arena, S->mem, S);
+    *out = S;
+    return ASTTS_OK;
+}
+
+int astts_lm_session_destroy(astts_lm_session_t* S) {
+    if (!S) return ASTTS_OK;
+    ASTTS_CHECK_HIP(hipStreamSynchronize(S->st));
+    ASTTS_CHECK_HIP(hipFree(S->mem));
+    delete S;
+    return ASTTS_OK;
+}
+
+int astts_lm_session_can_admit(const astts_lm_session_t* S, int32_t b, int32_t pos0, int32_t n_steps) {
+    return S ? S->plan.admissible(b, pos0, n_steps) : SESSION_ERR_ARG;
+}
+
+int astts_lm_session_admit(astts_lm_session_t* S, const float* logits0, void* const* kv_cache, const int32_t* key_start, int32_t t_max,
+                           int32_t b, int32_t pos0, int32_t n_steps, const float* uniforms, const int32_t* forced_tokens,
+                           int32_t eos_min_steps, const int32_t* eos_min_rows, int32_t* tokens_out, float* logits_out, int32_t* slot_out) {
+    ASTTS_REQUIRE(S && logits0 && kv_cache && uniforms && tokens_out && slot_out, ASTTS_ERR_INVALID, "astts_lm_session_admit: null argument");
+    ASTTS_REQUIRE(b >= 1 && n_steps >= 1 && pos0 >= 1 && pos0 + n_steps - 1 <= t_max, ASTTS_ERR_INVALID,
+                  "astts_lm_session_admit: b=%d pos0=%d n_steps=%d t_max=%d", b, pos0, n_steps, t_max);
+    const int slot = S->plan.admit(b, pos0, n_steps);
+    ASTTS_REQUIRE(slot >= 0, slot == SESSION_ERR_ARG ? ASTTS_ERR_INVALID : ASTTS_ERR_RANGE,
+                  "astts_lm_session_admit: %s (b=%d of %d rows, window %d of %d keys, %d groups active)",
+                  slot == SESSION_ERR_FULL ? "both slots are taken" : slot == SESSION_ERR_WINDOW ? "the window is longer than t_arena / 2"
+                                                                                                  : "no free rows beside the running group",
+                  b, S->plan.rows_max, pos0 + n_steps - 1, S->plan.half(), S->plan.n_active());
+    const SessionGroup& G = S->plan.g[slot];
+    const astts_lm_config_t& c = S->h->cfg;
+    KvPtrs src, dst;
+    for (int l = 0; l < kSessionMaxLayers; ++l) {
+        src.p[l] = l < c.layers ? (_Float16*)kv_cache[l] : nullptr;
+        dst.p[l] = l < c.layers ? S->arena.p[l] + (size_t)G.row0 * 2 * c.d : nullptr;
+    }
+    hipLaunchKernelGGL(lm_kv_admit, dim3(pos0, c.layers), dim3(256), 0, S->st, src, dst, key_start, S->kstart + G.row0, b, G.win_start,
+                       (int64_t)b * 2 * c.d, (int64_t)S->plan.rows_max * 2 * c.d, c.d / 4);
+    ASTTS_CHECK_LAUNCH();
+    ASTTS_CHECK_HIP(hipMemcpyAsync(S->ws.lg + (size_t)G.row0 * c.vocab_out, logits0, sizeof(float) * (size_t)b * c.vocab_out, hipMemcpyDeviceToDevice, S->st));
+    S->rows[slot] = RowGroup{G.row0, b, n_steps, 0, uniforms, forced_tokens, eos_min_steps, eos_min_rows, tokens_out, logits_out};
+    *slot_out = slot;
+    return ASTTS_OK;
+}
+
+int astts_lm_session_step(astts_lm_session_t* S, int32_t k, uint32_t* finished_mask_out) {
+    ASTTS_REQUIRE(S && k >= 1, ASTTS_ERR_INVALID, "astts_lm_session_step: null session or k=%d", k);
+    const astts_lm* h = S->h;
+    const astts_lm_config_t& c = h->cfg;
+    SessionPlan& P = S->plan;
+    uint32_t done = 0;
+    int left = k;
+    while (left > 0 && P.n_active() > 0) {
+        if (P.needs_rebase()) {
+            int r0 = 0, rows = 0;
+            P.cover(&r0, &rows);
+            const SessionPlan::Rebase rb = P.rebase();
+            ASTTS_REQUIRE(rb.n > 0 && rb.delta > 0, ASTTS_ERR_RANGE, "astts_lm_session_step: no legal rebase at position %d of %d", P.pos, P.t_arena);
+            KvPtrs kv;
+            for (int l = 0; l < kSessionMaxLayers; ++l) kv.p[l] = l < c.layers ? S->arena.p[l] + (size_t)r0 * 2 * c.d : nullptr;
+            hipLaunchKernelGGL(lm_kv_rebase, dim3(rb.n, c.layers), dim3(256), 0, S->st, kv, S->kstart + r0, rows, rb.src0, rb.delta,
+                               (int64_t)P.rows_max * 2 * c.d, c.d / 4);
+            ASTTS_CHECK_LAUNCH();
+            ++S->rebases;
+        }
+        const int q = P.quantum(left);
+        ASTTS_REQUIRE(q >= 1, ASTTS_ERR_RANGE, "astts_lm_session_step: no step fits at position %d of %d", P.pos, P.t_arena);
+        int r0 = 0, rows = 0;
+        P.cover(&r0, &rows);
+        RowWindow all(S, r0, rows);
+        all.k.pos0 = P.pos; all.k.s_begin = 0; all.k.s_end = q;
+        // groups in row order: the sampler's first group starts at the window's row 0
+        const int first = (P.g[0].active && (!P.g[1].active || P.g[0].row0 < P.g[1].row0)) ? 0 : 1;
+        for (int i = 0; i < SessionPlan::kGroups; ++i) {
+            const int gi = i == 0 ? first : 1 - first;
+            if (!P.g[gi].active) continue;
+            RowGroup r = S->rows[gi];
+            r.row0 = P.g[gi].row0 - r0;
+            r.s_off = P.g[gi].step;
+            all.k.g[all.k.n_groups++] = r;
+        }
+        // the range's last step: a group that ends there only samples; the forward pass then covers the rows of the groups that go on
+        int s0 = 0, srows = 0;
+        const bool narrower = P.cover(&s0, &srows, q - 1, true) && (s0 != r0 || srows != rows);
+        RowWindow rest(S, narrower ? s0 : r0, narrower ? srows : rows);
+        RUN(run_steps(c, all.k, all.v.lg, all.v.tok, [&](int pos) {
+            const bool tail = narrower && pos == P.pos + q - 1;
+            return step_v2(h, tail ? rest.k : all.k, tail ? rest.v : all.v, pos);
+        }));
+        done |= P.advance(q);
+        left -= q;
+    }
+    if (finished_mask_out) *finished_mask_out = done;
+    return ASTTS_OK;
+}
+
+int astts_lm_session_state(const astts_lm_session_t* S, int32_t* out6) {
+    ASTTS_REQUIRE(S && out6, ASTTS_ERR_INVALID, "astts_lm_session_state: null argument");
+    const SessionPlan& P = S->plan;
+    out6[0] = P.g[0].active | P.g[1].active << 1;
+    out6[1] = P.pos;
+    out6[2] = P.g[0].active ? P.g[0].n_steps - P.g[0].step : 0;
+    out6[3] = P.g[1].active ? P.g[1].n_steps - P.g[1].step : 0;
+    out6[4] = (int32_t)S->rebases;
+    out6[5] = P.half();
+    return ASTTS_OK;
 }
 
 }  // extern "C"

@@ -89,5 +89,20 @@ void lm_step_set_attrs();   // one-off hipFuncSetAttribute calls (outside any ca
 // bits 2.. = row tiles of 16 (1 or 2)
 int lm_gemv_variant(const GemvArgs& a);
 
+// One group of rows of a sampler launch (ops_audio.hip: ras_sample): the rows that sample the same step of the same decode.
+struct SampleGroup {
+    int32_t* history;             // [rows][hist_ld] token log: read (repetition window) and written at column hist_len
+    const float* uniforms;        // [rows][2]
+    const int32_t* forced;        // [rows][hist_ld] or null (teacher forcing)
+    const int32_t* eos_min_rows;  // [rows] or null: EOS may not be produced while hist_len < eos_min_rows[row]
+    int rows, row0;               // logits / out_tokens rows [row0, row0 + rows) of the launch
+    int hist_len, hist_ld;        // step index; row stride of history / forced
+    int eos_window;               // without eos_min_rows: 1 = EOS may not be produced at this step
+};
+// ONE ras_sample launch for one or two groups side by side (g[0].row0 == 0, g[1].row0 == g[0].rows).
+// logits [rows of the launch][vocab], out_tokens [rows of the launch] (clamped to eos_id - 1: the next step's embedding row).
+int ras_sample_groups_launch(const float* logits, int32_t* out_tokens, int vocab, int top_k, float top_p, int win_size, float tau_r,
+                             int eos_id, int eos_policy, const SampleGroup* g, int n_groups, hipStream_t st);
+
 
 }  // namespace astts

@@ -9,6 +9,7 @@
 // path can be driven by identical draws.  Replaces third-party cosyvoice.hifigan.generator /
 // cosyvoice.utils.common.ras_sampling arithmetic behind tts_with_rag.py:195.
 #include "common.h"
+#include "lm_step.h"
 #include "toplist.h"
 #include "xlane.h"
 
@@ -189,6 +190,16 @@ struct SampleArgs {
     const int* eos_min_rows;  // when set: EOS is masked for row b while hist_len < eos_min_rows[b] (ragged batches)
     int b, v, hist_len, hist_ld, top_k, win, eos, ignore_eos;
     float top_p, tau_r;
+    // a SECOND group of rows in the same launch (a decode session, lm_engine.hip: two batches that share one chain).  split > 0: blocks
+    // [0, split) are the first group, blocks [split, gridDim.x) the second with its own step index, token log, uniforms, forced tokens
+    // and EOS window (indexed by block - split).  logits and out are indexed by the block for both.
+    int split;
+    const int* history2;
+    const float* u2;
+    int* hist_w2;
+    const int* forced2;
+    const int* eos_min_rows2;
+    int hist_len2, hist_ld2, ignore_eos2;
 };
 
 // 1024 threads per row: every pass over the 4097 logits is 4-5 elements per thread (the kernel is a chain of short
@@ -212,11 +223,17 @@ __global__ __launch_bounds__(RS_NT) void ras_sample(const float* p_logits, const
     __shared__ unsigned hist[3][2048];
     __shared__ int s_sel_bin[3], s_sel_rem[3], s_cnt;
     const int bb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    int lr = bb;                       // the row inside its group: index of everything but logits / out
+    if (a.split > 0 && bb >= a.split) {
+        lr = bb - a.split;
+        a.history = a.history2; a.u = a.u2; a.hist_w = a.hist_w2; a.forced = a.forced2; a.eos_min_rows = a.eos_min_rows2;
+        a.hist_len = a.hist_len2; a.hist_ld = a.hist_ld2; a.ignore_eos = a.ignore_eos2;
+    }
     const float* lg = a.logits + (int64_t)bb * a.v;
     // ignore_eos: bit 0 = EOS may not be produced at this step (scalar form; with eos_min_rows the window is per row), bit 1 = the
     // policy inside that window: 0 "mask" (the EOS logit is removed before the softmax), 1 "reject" (upstream's sampling_ids: draw
     // again until the token is not EOS -- EOS keeps its probability, its place in the nucleus and its share of top_p / top_k)
-    const bool eos_window = a.eos_min_rows ? (a.hist_len < a.eos_min_rows[bb]) : ((a.ignore_eos & 1) != 0);
+    const bool eos_window = a.eos_min_rows ? (a.hist_len < a.eos_min_rows[lr]) : ((a.ignore_eos & 1) != 0);
     const bool reject = eos_window && (a.ignore_eos & 2) != 0;
     const bool mask_eos = eos_window && !reject;
     // operands of the LAST phases, requested now: the two uniforms and the repetition window of the token log were dependent
@@ -226,9 +243,9 @@ __global__ __launch_bounds__(RS_NT) void ras_sample(const float* p_logits, const
     float u_first = 0.0f, u_second = 0.0f;
     int hwin = -1;
     if (wid == 0) {
-        u_first = a.u[bb * 2];
-        u_second = a.u[bb * 2 + 1];
-        if (win_in_wave && h0 + lane < a.hist_len) hwin = a.history[(int64_t)bb * a.hist_ld + h0 + lane];
+        u_first = a.u[lr * 2];
+        u_second = a.u[lr * 2 + 1];
+        if (win_in_wave && h0 + lane < a.hist_len) hwin = a.history[(int64_t)lr * a.hist_ld + h0 + lane];
     }
     for (int i = tid; i < 3 * 2048; i += RS_NT) (&hist[0][0])[i] = 0u;
     if (tid == 0) s_cnt = 0;
@@ -391,7 +408,7 @@ __global__ __launch_bounds__(RS_NT) void ras_sample(const float* p_logits, const
             } else {
                 for (int i0 = h0; i0 < a.hist_len; i0 += 64) {
                     const int i = i0 + lane;
-                    const bool hit = i < a.hist_len && a.history[(int64_t)bb * a.hist_ld + i] == t;
+                    const bool hit = i < a.hist_len && a.history[(int64_t)lr * a.hist_ld + i] == t;
                     rep += __popcll(__ballot(hit));
                 }
             }
@@ -433,7 +450,7 @@ __global__ __launch_bounds__(RS_NT) void ras_sample(const float* p_logits, const
                 const int wl = a.hist_len - h0;             // window tokens sit on lanes 0 .. wl - 1 of hwin
                 for (int j = 0; j < wl; ++j) repc += __builtin_amdgcn_readlane(hwin, j) == ir_l ? 1 : 0;
             } else {
-                for (int i = h0; i < a.hist_len; ++i) repc += a.history[(int64_t)bb * a.hist_ld + i] == ir_l ? 1 : 0;
+                for (int i = h0; i < a.hist_len; ++i) repc += a.history[(int64_t)lr * a.hist_ld + i] == ir_l ? 1 : 0;
             }
             const bool rep_l = (float)repc >= (float)a.win * a.tau_r;
             const unsigned long long direct = __ballot(lane < cnt && ir_l != a.eos && !rep_l);      // neither EOS nor repeated
@@ -500,8 +517,8 @@ __global__ __launch_bounds__(RS_NT) void ras_sample(const float* p_logits, const
     __syncthreads();
     if (tid == 0) {
         int tok = s_tok;
-        if (a.forced) tok = a.forced[(int64_t)bb * a.hist_ld + a.hist_len];
-        if (a.hist_w) a.hist_w[(int64_t)bb * a.hist_ld + a.hist_len] = tok;
+        if (a.forced) tok = a.forced[(int64_t)lr * a.hist_ld + a.hist_len];
+        if (a.hist_w) a.hist_w[(int64_t)lr * a.hist_ld + a.hist_len] = tok;
         a.out[bb] = (a.clamp_out >= 0 && tok > a.clamp_out) ? a.clamp_out : tok;
     }
 }
@@ -649,6 +666,32 @@ __global__ __launch_bounds__(256) void whisper_floor(float* __restrict__ x, cons
     }
 }
 
+// The engine's sampler launch: one or two groups of rows (lm_step.h: SampleGroup) in ONE launch.
+int ras_sample_groups_launch(const float* logits, int32_t* out_tokens, int vocab, int top_k, float top_p, int win_size, float tau_r,
+                                    int eos_id, int eos_policy, const SampleGroup* g, int n_groups, hipStream_t stream) {
+    ASTTS_REQUIRE(logits && out_tokens && g && (n_groups == 1 || n_groups == 2), ASTTS_ERR_INVALID, "ras_sample_groups: null pointer or %d groups", n_groups);
+    ASTTS_REQUIRE(vocab >= 2 && vocab <= 15000 && top_k >= 1 && top_k <= 64, ASTTS_ERR_INVALID, "ras_sample_groups: bad shape vocab=%d top_k=%d", vocab, top_k);
+    ASTTS_REQUIRE(!eos_policy || (eos_id >= 0 && eos_id < vocab), ASTTS_ERR_RANGE, "ras_sample_groups: eos_id=%d outside [0, %d) with the reject policy", eos_id, vocab);
+    for (int i = 0; i < n_groups; ++i)
+        ASTTS_REQUIRE(g[i].history && g[i].uniforms && g[i].rows >= 1 && g[i].hist_len >= 0 && g[i].hist_len < g[i].hist_ld, ASTTS_ERR_INVALID,
+                      "ras_sample_groups: group %d: null pointer, rows=%d or hist_len=%d of %d", i, g[i].rows, g[i].hist_len, g[i].hist_ld);
+    ASTTS_REQUIRE(g[0].row0 == 0 && (n_groups == 1 || g[1].row0 == g[0].rows), ASTTS_ERR_INVALID, "ras_sample_groups: the groups' rows are not side by side from row 0");
+    const int pol = eos_policy ? 2 : 0;
+    SampleArgs a{logits, g[0].history, g[0].uniforms, out_tokens, g[0].history, g[0].forced, eos_id - 1, g[0].eos_min_rows, g[0].rows, vocab, g[0].hist_len,
+                 g[0].hist_ld, top_k, win_size, eos_id, (g[0].eos_window ? 1 : 0) | pol, top_p, tau_r,
+                 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+    int blocks = g[0].rows;
+    if (n_groups == 2) {
+        a.split = g[1].row0; a.history2 = g[1].history; a.u2 = g[1].uniforms; a.hist_w2 = g[1].history; a.forced2 = g[1].forced;
+        a.eos_min_rows2 = g[1].eos_min_rows; a.hist_len2 = g[1].hist_len; a.hist_ld2 = g[1].hist_ld; a.ignore_eos2 = (g[1].eos_window ? 1 : 0) | pol;
+        blocks = g[1].row0 + g[1].rows;
+    }
+    hipLaunchKernelGGL(ras_sample, dim3(blocks), dim3(RS_NT), (size_t)((vocab + 15) & ~15) * sizeof(float), stream, a.logits, a.eos_min_rows, a.v,
+                       a.hist_len, a.eos, a.ignore_eos, a);
+    ASTTS_CHECK_LAUNCH();
+    return ASTTS_OK;
+}
+
 }  // namespace astts
 
 using namespace astts;
@@ -706,7 +749,8 @@ int astts_op_ras_sample(const float* logits, const int32_t* history, const float
                   "astts_op_ras_sample: bad shape b=%d vocab=%d top_k=%d", b, vocab, top_k);
     // the reject policy (bit 1) reads and clears prob[eos_id] in LDS: the id must be a vocabulary entry (the mask policy only compares with it)
     ASTTS_REQUIRE(!(ignore_eos & 2) || (eos_id >= 0 && eos_id < vocab), ASTTS_ERR_RANGE, "astts_op_ras_sample: eos_id=%d outside [0, %d) with the reject policy", eos_id, vocab);
-    SampleArgs a{logits, history, uniforms, out_tokens, nullptr, nullptr, -1, nullptr, b, vocab, hist_len, hist_ld, top_k, win_size, eos_id, ignore_eos, top_p, tau_r};
+    SampleArgs a{logits, history, uniforms, out_tokens, nullptr, nullptr, -1, nullptr, b, vocab, hist_len, hist_ld, top_k, win_size, eos_id, ignore_eos, top_p, tau_r,
+                 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
     hipLaunchKernelGGL(ras_sample, dim3(b), dim3(RS_NT), (size_t)((vocab + 15) & ~15) * sizeof(float), (hipStream_t)stream, a.logits, a.eos_min_rows, a.v,
                        a.hist_len, a.eos, a.ignore_eos, a);
     ASTTS_CHECK_LAUNCH();
@@ -722,13 +766,11 @@ int astts_op_ras_sample_ex(const float* logits, int32_t* history, const float* u
     ASTTS_REQUIRE(b >= 1 && vocab >= 2 && vocab <= 15000 && top_k >= 1 && top_k <= 64 && hist_len >= 0 && hist_len < hist_ld,
                   ASTTS_ERR_INVALID, "astts_op_ras_sample_ex: bad shape b=%d vocab=%d top_k=%d hist_len=%d", b, vocab, top_k, hist_len);
     ASTTS_REQUIRE(!(ignore_eos & 2) || (eos_id >= 0 && eos_id < vocab), ASTTS_ERR_RANGE, "astts_op_ras_sample_ex: eos_id=%d outside [0, %d) with the reject policy", eos_id, vocab);
-    SampleArgs a{logits, history, uniforms, out_tokens, history, forced, eos_id - 1, eos_min_rows, b, vocab, hist_len, hist_ld, top_k, win_size,
-                 eos_id, ignore_eos, top_p, tau_r};
-    hipLaunchKernelGGL(ras_sample, dim3(b), dim3(RS_NT), (size_t)((vocab + 15) & ~15) * sizeof(float), (hipStream_t)stream, a.logits, a.eos_min_rows, a.v,
-                       a.hist_len, a.eos, a.ignore_eos, a);
-    ASTTS_CHECK_LAUNCH();
-    return ASTTS_OK;
+    const astts::SampleGroup g{history, uniforms, forced, eos_min_rows, b, 0, hist_len, hist_ld, ignore_eos & 1};
+    return astts::ras_sample_groups_launch(logits, out_tokens, vocab, top_k, top_p, win_size, tau_r, eos_id, (ignore_eos >> 1) & 1, &g, 1,
+                                           (hipStream_t)stream);
 }
+
 
 
 int astts_op_resample_poly(const float* x, const float* kern, float* y, int32_t b, int64_t n_in, int64_t n_out, int32_t up, int32_t down,
