@@ -33,6 +33,7 @@ import torch
 from .. import audio
 from ..frontend import Frontend, PromptFeatures, text_normalize
 from ..synth.config import SynthConfig
+from ..synth.decode import record_streams
 
 
 def load_wav(path: str, target_sr: int) -> torch.Tensor:
@@ -54,10 +55,9 @@ class _LmTokenStream:
         self.stream = stream
         dev = lm.device
         stream.wait_stream(torch.cuda.current_stream(dev))          # the prefill ran on the caller's stream
-        for t in lm.prefill_tensors(state) + [uniforms]:
-            t.record_stream(stream)
+        record_streams(lm.prefill_tensors(state) + [uniforms], stream)
         with torch.cuda.stream(stream):
-            self.ctx = lm.decode_begin(state, uniforms, ignore_eos=max_len if fixed else min_len)
+            self.job = lm.decode_begin(state, uniforms, ignore_eos=max_len if fixed else min_len)
         self.host = torch.empty((max_len,), dtype=torch.int32).pin_memory()
         self.ranges = list(ranges)                                   # [(s_begin, s_end)] covering [0, max_len)
         self.events = [torch.cuda.Event() for _ in self.ranges]
@@ -87,8 +87,8 @@ class _LmTokenStream:
                             self._cv.wait()
                     if self.cancel:
                         break
-                    self.lm.decode_range(self.ctx, e)
-                    self.host[b:e].copy_(self.ctx["toks"][0, b:e], non_blocking=True)
+                    self.lm.decode_range(self.job, e)
+                    self.host[b:e].copy_(self.job.toks[0, b:e], non_blocking=True)
                     self.events[k].record(self.stream)
                     self.issued[k].set()
         except BaseException as e:      # noqa: BLE001  (re-raised in wait())

@@ -57,7 +57,7 @@ int astts_prof_enable(int32_t kind, int32_t on, int32_t max_launches);
 int astts_prof_read(int32_t kind, double* ms_sum, int64_t* launches, double* work_sum, int64_t* dropped);
 /* One 64-thread workgroup that busy-waits `microseconds` on `stream`.  HIP multiplexes its streams onto a few
  * hardware queues; two streams that share one never overlap.  The pipelined synthesis uses this probe to pick streams
- * that really run concurrently (astts/synth/model.py: PipelinedSynth). */
+ * that really run concurrently (astts/synth/pipeline.py: PipelinedSynth). */
 int astts_stream_spin(int32_t microseconds, astts_stream_t stream);
 /* `count` dependent busy-wait launches (`blocks` workgroups, `microseconds` each): a launch-chain stand-in for stream probing */
 int astts_stream_chain(int32_t count, int32_t microseconds, int32_t blocks, astts_stream_t stream);

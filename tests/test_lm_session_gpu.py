@@ -1,4 +1,4 @@
-"""Decode sessions (csrc/lm_engine.hip: astts_lm_session_*, astts.synth.model.LmSession): a batch that JOINS a running decode chain
+"""Decode sessions (csrc/lm_engine.hip: astts_lm_session_*, astts.synth.decode.LmSession): a batch that JOINS a running decode chain
 gets, bit for bit, the logits (teacher forced) and the tokens (free running) of the same batch decoded alone by astts_lm_decode --
 torch.equal, no tolerance: every decode kernel is row-independent and the attention only sees positions relative to the query."""
 import dataclasses
@@ -60,20 +60,20 @@ def _joined(lm, batches, joins, forced, rows_max, t_arena):
             i = pending.pop(0)
             B = batches[i]
             st = lm.prefill(B["pre"], B["steps"], B["ks"])
-            assert sess.can_admit(B["b"], st["s0"], B["steps"]), (i, t)
+            assert sess.can_admit(B["b"], st.s0, B["steps"]), (i, t)
             ctx[i] = sess.admit(st, B["u"], B["ignore_eos"], B["forced"] if flags[i] else None, return_logits=True)
             t = max(t, joins[i])
         k = min(sess.steps_left())
         if pending:
             k = min(k, joins[pending[0]] - t)
         done = sess.step(k)
-        assert all(c["next"] == c["n_steps"] for c in done)
+        assert all(c.next == c.n_steps for c in done)
         t += k
     state = (ctypes.c_int32 * 6)()
     assert sess._lib.astts_lm_session_state(sess._h, state) == 0
     torch.cuda.synchronize()
     sess.close()
-    return [(c["toks"], c["logits"]) for c in ctx], list(state)
+    return [(c.toks, c.logits) for c in ctx], list(state)
 
 
 def _assert_joined_equals_solo(lm, batches, joins, rows_max, t_arena=None):

@@ -376,7 +376,7 @@ def test_wide_engine_logits_match_oracle(size, b):
     ctx = lm.decode_begin(st, u.to(DEV), True, None)
     lm.decode_range(ctx, 3)
     lm.decode_range(ctx)
-    assert torch.equal(ctx["toks"], t_w)
+    assert torch.equal(ctx.toks, t_w)
     # inside the wide engine a row does not depend on the rows beside it (gemm_rows / attn_relpos_rows sum a row's terms in an order of
     # its own): the first 36 rows as a wide batch of their own
     if b >= 72:
@@ -405,6 +405,6 @@ def test_ranges_of_steps_equal_one_call(engine):
         lm.decode_range(ctx, 4)
         lm.decode_range(ctx)
         toks, logits = lm.decode_prefilled(lm.prefill(pre, steps), u, True, None, return_logits=True)
-    assert ctx["next"] == steps
-    assert torch.equal(ctx["toks"], toks) and torch.equal(ctx["logits"], logits)
+    assert ctx.next == steps
+    assert torch.equal(ctx.toks, toks) and torch.equal(ctx.logits, logits)
     assert int(toks.min()) >= 0 and int(toks.max()) < cfg.speech_vocab
