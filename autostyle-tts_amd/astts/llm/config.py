@@ -37,7 +37,7 @@ class LlamaShape:
 
     @staticmethod
     def tiny() -> "LlamaShape":
-        """Small everywhere except the head dimension (128, as the real model: the attention kernel is built for it)."""
+        """Small everywhere except the head dimension (128, as the 3B model)."""
         return LlamaShape(vocab=512, hidden=512, layers=3, heads=4, kv_heads=2, ffn=1024, eos_token_id=2, bos_token_id=1)
 
     @staticmethod
@@ -51,6 +51,28 @@ class LlamaShape:
         """Qwen2.5-7B's differences from Llama in their smallest form: q / k / v biases, plain RoPE at theta 1e6, an untied head and a
         GQA group of 7 (7 query heads on 1 KV head).  896 and 1152 are multiples of 128 and 64 but not of 256."""
         return LlamaShape(vocab=512, hidden=896, layers=3, heads=7, kv_heads=1, ffn=1152, rms_eps=1e-6, rope_theta=1e6,
+                          max_positions=32768, tie_embeddings=False, eos_token_id=2, bos_token_id=1, model_type="qwen2", qkv_bias=True,
+                          rope_type="default")
+
+    @staticmethod
+    def llama32_1b() -> "LlamaShape":
+        """Llama-3.2-1B's config.json: head dimension 64 (the attention kernels are built for 64 and 128), a KV group of 4."""
+        return LlamaShape(hidden=2048, layers=16, heads=32, kv_heads=8, head_dim=64)
+
+    @staticmethod
+    def tiny64() -> "LlamaShape":
+        """``tiny()`` at head dimension 64: 8 / 2 heads (a KV group of 4) over the same widths."""
+        return LlamaShape(vocab=512, hidden=512, layers=3, heads=8, kv_heads=2, head_dim=64, ffn=1024, eos_token_id=2, bos_token_id=1)
+
+    @staticmethod
+    def wide64() -> "LlamaShape":
+        """Llama-3.2-1B's widths (hidden 2048, 32 / 8 heads of 64, FFN 8192) with two layers and a small vocabulary, as ``wide()`` is to the 3B."""
+        return LlamaShape(vocab=4096, hidden=2048, layers=2, heads=32, kv_heads=8, head_dim=64, eos_token_id=2, bos_token_id=1)
+
+    @staticmethod
+    def qwen2_tiny64() -> "LlamaShape":
+        """``qwen2_tiny()`` with 14 / 2 heads of 64 (Qwen2.5-0.5B's geometry): the same widths, a KV group of 7 at head dimension 64."""
+        return LlamaShape(vocab=512, hidden=896, layers=3, heads=14, kv_heads=2, head_dim=64, ffn=1152, rms_eps=1e-6, rope_theta=1e6,
                           max_positions=32768, tie_embeddings=False, eos_token_id=2, bos_token_id=1, model_type="qwen2", qkv_bias=True,
                           rope_type="default")
 

@@ -1,7 +1,7 @@
 """The Llama-3.2 decoder on the GPU: weights, RoPE tables and the layer stack in its two layouts (batch-major over right-padded
 texts; time-major over left-padded prompts with a KV cache).  astts.llm.embedder.LlamaEmbedder builds the reference's calls on it.
 Every tensor operation is a HIP kernel of libastts.so (GEMMs: the MFMA family of csrc/ops_gemm.hip with fp16 activations;
-RMSNorm / RoPE / causal GQA attention at head_dim 128 / SwiGLU / mean-pool: csrc/ops_llm.hip).  fp16 weights and MFMA
+RMSNorm / RoPE / causal GQA attention at head_dim 64 or 128 / SwiGLU / mean-pool: csrc/ops_llm.hip).  fp16 weights and MFMA
 operands, fp32 residual stream, norms and softmax.  Parity: tests/test_llm_gpu.py against fixtures produced by transformers (fp32).
 
 ``int8=True`` runs the reference's own numerics instead (src/search_milvus.py:47-62: a PEFT LoRA adapter over LLM.int8 weights):
@@ -67,8 +67,8 @@ class LlamaDecoder:
     def __init__(self, state: dict, cfg: LlamaShape, device=None, int8: bool = False, lora=None, int8_threshold: float = 6.0, rope_len: int = 576):
         if not torch.cuda.is_available():
             raise RuntimeError("astts.llm needs a ROCm GPU; there is no CPU fallback in the product path")
-        if cfg.head_dim != 128:
-            raise ValueError("LlamaEmbedder: the attention kernel is built for head_dim 128 (Llama-3.2)")
+        if cfg.head_dim not in (64, 128):
+            raise ValueError(f"LlamaDecoder: head_dim {cfg.head_dim}: the attention kernels are built for 64 and 128")
         self.cfg = cfg
         self.device = dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.mfma_attention = os.environ.get("ASTTS_LLM_ATTN", "mfma") != "valu"
@@ -175,7 +175,7 @@ class LlamaDecoder:
 
     def hidden_cached(self, x: torch.Tensor, cache: List[torch.Tensor], pos0: int, start: torch.Tensor, seg) -> torch.Tensor:
         """x fp32 [T', B, hidden] = the new positions pos0 .. pos0 + T' - 1 of LEFT-padded rows, time-major -> final-norm hidden of the
-        LAST of them [B, hidden].  ``cache``: per layer fp16 ``[T_max, B, 2 * kv_heads * 128]``, K (rotated) | V; the rows of a step are
+        LAST of them [B, hidden].  ``cache``: per layer fp16 ``[T_max, B, 2 * kv_heads * head_dim]``, K (rotated) | V; the rows of a step are
         contiguous in it.  ``start[b]`` (int32 [B]): the time step of row b's first token; it masks the row's pad keys and shifts its RoPE
         positions so that that token has position 0, as in the one-at-a-time reference run."""
         cfg = self.cfg

@@ -5,8 +5,9 @@
 // file holds what a Llama block needs besides them:
 //   rmsnorm_rows       x * rsqrt(mean(x^2) + eps) * w, fp32 residual stream in, fp16 MFMA operand out (one wave per row)
 //   rope_llama         rotate-half RoPE on the q and k heads of a fused q|k|v buffer, in place (fp32 math on fp16 data)
-//   attn_causal_gqa    causal grouped-query attention at head dimension 128 (the flash kernel of ops_attention.hip is
-//                      built around 64): 32 queries x 8 lanes per workgroup, K / V tiles staged in LDS, online softmax.
+//   attn_causal_gqa    causal grouped-query attention at head dimension 128 or 64 (the flash kernel of ops_attention.hip has
+//                      no KV groups, cache strides or padding masks): 32 queries x 8 lanes per workgroup, K / V tiles staged
+//                      in LDS, online softmax.  attn_gqa_mfma is the same operator on the matrix cores.
 //                      Prompts are <= 512 tokens (src/search_milvus.py:92): per layer ~1 % of the projection flops.
 //   swiglu             silu(gate) * up on the fused gate|up projection
 //   mean_pool          masked mean over the tokens of each text (the embedding itself)
@@ -141,21 +142,89 @@ __global__ __launch_bounds__(256) void attn_causal_gqa(const _Float16* __restric
     }
 }
 
+// The same kernel at head_dim 64: thread (qi, sub) owns dims [8 sub, 8 sub + 8) of query qi.  Beside the 128 kernel, not a template over
+// both: how the compiler contracts o * sc + p * v into fma differs from element to element of the 128 kernel, and its text is left as
+// it is so that it keeps computing the same bits.
+static constexpr int GA_D64 = 64;
 
-// ---- causal GQA attention on the matrix cores, head_dim 128 (round 5; the VALU kernel above stays as the second implementation the
-// tests compare with).  The skeleton of attn_mha_flash (ops_attention.hip) at twice the head dimension:
+__global__ __launch_bounds__(256) void attn_causal_gqa64(const _Float16* __restrict__ q, const _Float16* __restrict__ k,
+                                                         const _Float16* __restrict__ v, const int* __restrict__ lens,
+                                                         _Float16* __restrict__ out, int t, int heads, int kv_heads, int ldq, int ldk,
+                                                         int ldo, float scale) {
+    __shared__ __attribute__((aligned(16))) _Float16 sk[GA_K][GA_D64 + 8];
+    __shared__ __attribute__((aligned(16))) _Float16 sv[GA_K][GA_D64 + 8];
+    const int tid = threadIdx.x, qi = tid >> 3, sub = tid & 7;
+    const int q0 = blockIdx.x * GA_Q, head = blockIdx.y, b = blockIdx.z;
+    const int kvh = head / (heads / kv_heads);
+    const int len = lens ? min(lens[b], t) : t;
+    const int qrow = q0 + qi;
+    const bool qvalid = qrow < len;
+    float qf[8];
+    {
+        const half8 a = *reinterpret_cast<const half8*>(q + ((int64_t)b * t + min(qrow, t - 1)) * ldq + head * GA_D64 + sub * 8);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qf[e] = (float)a[e] * scale;
+    }
+    float m_run = -INFINITY, l_run = 0.0f, o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = 0.0f;
+    const int kend = min(len, q0 + GA_Q);                   // causal: no key beyond the tile's last query
+    for (int k0 = 0; k0 < kend; k0 += GA_K) {
+        __syncthreads();
+        {   // stage 32 keys x 64 dims of K and V: thread -> (key = tid >> 3, 8 dims)
+            const int kr = min(k0 + qi, t - 1);
+            const int64_t at = ((int64_t)b * t + kr) * ldk + kvh * GA_D64 + sub * 8;
+            *reinterpret_cast<half8*>(&sk[qi][sub * 8]) = *reinterpret_cast<const half8*>(k + at);
+            *reinterpret_cast<half8*>(&sv[qi][sub * 8]) = *reinterpret_cast<const half8*>(v + at);
+        }
+        __syncthreads();
+        const int nk = min(GA_K, kend - k0);
+        for (int j = 0; j < nk; ++j) {
+            const half8 ka = *reinterpret_cast<const half8*>(&sk[j][sub * 8]);
+            float s = 0.0f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s += qf[e] * (float)ka[e];
+            s += __shfl_xor(s, 1, 64);
+            s += __shfl_xor(s, 2, 64);
+            s += __shfl_xor(s, 4, 64);
+            if (k0 + j > qrow) continue;                     // causal mask (uniform over the 8 lanes of a query)
+            const float m_new = fmaxf(m_run, s);
+            const float sc = m_run == -INFINITY ? 0.0f : __expf(m_run - m_new);
+            const float p = __expf(s - m_new);
+            l_run = l_run * sc + p;
+            const half8 va = *reinterpret_cast<const half8*>(&sv[j][sub * 8]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = o[e] * sc + p * (float)va[e];
+            m_run = m_new;
+        }
+    }
+    if (qrow < t) {
+        const float inv = (qvalid && l_run > 0.0f) ? 1.0f / l_run : 0.0f;
+        half8 a;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[e] = (_Float16)(o[e] * inv);
+        *reinterpret_cast<half8*>(out + ((int64_t)b * t + qrow) * ldo + head * GA_D64 + sub * 8) = a;
+    }
+}
+
+
+// ---- causal GQA attention on the matrix cores, head_dim D = 128 or 64 (the VALU kernel above stays as the second implementation the
+// tests compare with).  The skeleton of attn_mha_flash (ops_attention.hip):
 //   workgroup = 4 waves x 32 queries of one (head, batch row); keys in tiles of 64 through LDS (K row-major, V transposed);
-//   S^T = K Q^T with v_mfma_f32_32x32x16_f16 (8 k-steps over the 128 dims) so that the QUERY sits on the lane: the online softmax is
-//   lane-local (one cross-half exchange) in the log2 domain, P^T feeds O^T += V^T P^T straight from the accumulator registers (the
-//   k order inside a step follows the accumulator layout: element j of lane half h is key 16 s + 8 (j >> 2) + 4 h + (j & 3)).
+//   S^T = K Q^T with v_mfma_f32_32x32x16_f16 (D / 16 k-steps: 8 at 128, 4 at 64) so that the QUERY sits on the lane: the online softmax
+//   is lane-local (one cross-half exchange) in the log2 domain, P^T feeds O^T += V^T P^T (D / 32 dimension tiles) straight from the
+//   accumulator registers (the k order inside a step follows the accumulator layout: element j of lane half h is key
+//   16 s + 8 (j >> 2) + 4 h + (j & 3)).
 // Generalised for the generation path: explicit (batch, time) strides (time-major KV cache), `pos0` = key index of query 0 (a decode
 // step's single query attends the whole cache), `key_start` (left-padded prompts: keys before a row's first token are masked), `lens`
-// (right-padded batches: keys at or beyond are masked, queries at or beyond produce zeros).  The three query heads of a KV group are
-// separate workgroups (K / V tiles come from L2 the second and third time: prompts are <= 512 tokens).
+// (right-padded batches: keys at or beyond are masked, queries at or beyond produce zeros).  The query heads of a KV group are
+// separate workgroups (K / V tiles come from L2 the second and later times: prompts are <= 512 tokens).
+// LDS rows: K and the epilogue's output rows are D + 8 halfs (136 at 128: 68 dwords, 16 lanes x 16 B cover the 64 banks once; 72 at 64:
+// 36 dwords, as FA_KS, the 16-byte reads of 8 consecutive rows start 4 banks apart and tile the 64 banks once); a V^T row holds the
+// tile's 64 keys whatever D is, so its stride stays 68 (as FA_VS: the 32 dims a half-wave reads with ds_read_b64 start on 32
+// different even banks).
 static constexpr int GM_KT = 64;    // keys per staged tile
-static constexpr int GM_KS = 136;   // halfs per K row in LDS (128 + 8): 68 dwords, 16 lanes x 16 B cover the 64 banks once
-static constexpr int GM_VS = 68;    // halfs per V^T row (as FA_VS: the 32 dims a half-wave reads with ds_read_b64 start on 32 different even banks)
-static constexpr int GM_OS = 136;   // halfs per output row of the epilogue transpose (aliases the K / V^T images)
+static constexpr int GM_VS = 68;    // halfs per V^T row
 
 struct GqaArgs {
     const _Float16* q;
@@ -169,10 +238,18 @@ struct GqaArgs {
     float scale;
 };
 
+template <int D>
 __global__ __launch_bounds__(256) void attn_gqa_mfma(GqaArgs a) {
-    __shared__ __attribute__((aligned(16))) _Float16 smem[GM_KT * GM_KS + GA_D * GM_VS];      // 17 408 + 17 408 bytes
+    constexpr int KS = D + 8;        // halfs per K row in LDS
+    constexpr int OS = D + 8;        // halfs per output row of the epilogue transpose (aliases the K / V^T images)
+    constexpr int NS = D / 16;       // k-steps of S^T
+    constexpr int NDT = D / 32;      // dimension tiles of O^T
+    constexpr int KH = D / 32;       // half8 pieces of a K row one thread stages
+    constexpr int VH = D / 64;       // half8 pieces of each key of a pair one thread stages
+    constexpr int IMG = GM_KT * KS + D * GM_VS, EPI = 128 * OS;      // 128: 17 408 + 17 408 bytes = the epilogue's; 64: 17 920, epilogue 18 432
+    __shared__ __attribute__((aligned(16))) _Float16 smem[IMG > EPI ? IMG : EPI];
     _Float16* ks = smem;
-    _Float16* vt = smem + GM_KT * GM_KS;
+    _Float16* vt = smem + GM_KT * KS;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int c = lane & 31, hh = lane >> 5;
     const int head = blockIdx.y, b = blockIdx.z;
@@ -181,56 +258,57 @@ __global__ __launch_bounds__(256) void attn_gqa_mfma(GqaArgs a) {
     const int len = a.lens ? min(a.lens[b], a.tk) : a.tk;
     const int kstart = a.key_start ? max(a.key_start[b], 0) : 0;
     const int kend = min(len, a.pos0 + min(qblk + 128, a.tq));       // causal: no key beyond the block's last query
-    const _Float16* qp = a.q + (int64_t)b * a.sqb + head * GA_D;
-    const _Float16* kp = a.k + (int64_t)b * a.skb + kvh * GA_D;
-    const _Float16* vp = a.v + (int64_t)b * a.skb + kvh * GA_D;
+    const _Float16* qp = a.q + (int64_t)b * a.sqb + head * D;
+    const _Float16* kp = a.k + (int64_t)b * a.skb + kvh * D;
+    const _Float16* vp = a.v + (int64_t)b * a.skb + kvh * D;
 
     // Q fragments (B operand of S^T = K Q^T): lane (c, hh) holds Q[q0 + c][16 s + 8 hh + j] * scale * log2(e)
-    half8 qf[8];
+    half8 qf[NS];
     {
         const _Float16* qr = qp + (int64_t)min(q0 + c, a.tq - 1) * a.sqt;
         const float sc = a.scale * 1.44269504088896341f;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
+        for (int s = 0; s < NS; ++s) {
             const half8 x = *reinterpret_cast<const half8*>(qr + 16 * s + 8 * hh);
 #pragma unroll
             for (int i = 0; i < 8; ++i) qf[s][i] = (_Float16)((float)x[i] * sc);
         }
     }
-    float16v ot[4];
+    float16v ot[NDT];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
         for (int e = 0; e < 16; ++e) ot[dt][e] = 0.0f;
     float m_run = -INFINITY, l_run = 0.0f;
-    // staging: K -- key row skey, 32 dims from sd0; V -- key PAIR vkp, 16 dims from vd0, written transposed as whole dwords
-    const int skey = tid >> 2, sd0 = (tid & 3) * 32;
-    const int vkp = tid >> 3, vd0 = (tid & 7) * 16;
-    half8 rk[4], rv[4];
+    // staging: K -- key row skey, D / 4 dims from sd0; V -- key PAIR vkp, D / 8 dims from vd0, written transposed as whole dwords
+    const int skey = tid >> 2, sd0 = (tid & 3) * (D / 4);
+    const int vkp = tid >> 3, vd0 = (tid & 7) * (D / 8);
+    half8 rk[KH], rv[2 * VH];
     auto prefetch = [&](int j0) {
         const int j = min(j0 + skey, a.tk - 1);                       // clamped; masked in the scores
         const _Float16* p = kp + (int64_t)j * a.skt + sd0;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) rk[i] = *reinterpret_cast<const half8*>(p + 8 * i);
+        for (int i = 0; i < KH; ++i) rk[i] = *reinterpret_cast<const half8*>(p + 8 * i);
         const int jv0 = min(j0 + 2 * vkp, a.tk - 1), jv1 = min(j0 + 2 * vkp + 1, a.tk - 1);
         const _Float16* p0 = vp + (int64_t)jv0 * a.skt + vd0;
         const _Float16* p1 = vp + (int64_t)jv1 * a.skt + vd0;
-        rv[0] = *reinterpret_cast<const half8*>(p0);
-        rv[1] = *reinterpret_cast<const half8*>(p0 + 8);
-        rv[2] = *reinterpret_cast<const half8*>(p1);
-        rv[3] = *reinterpret_cast<const half8*>(p1 + 8);
+#pragma unroll
+        for (int i = 0; i < VH; ++i) {
+            rv[i] = *reinterpret_cast<const half8*>(p0 + 8 * i);
+            rv[VH + i] = *reinterpret_cast<const half8*>(p1 + 8 * i);
+        }
     };
     const int jfirst = (kstart / GM_KT) * GM_KT;                      // tiles wholly before the row's first token are skipped
     if (jfirst < kend) prefetch(jfirst);
     for (int j0 = jfirst; j0 < kend; j0 += GM_KT) {
         __syncthreads();
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<half8*>(&ks[skey * GM_KS + sd0 + 8 * i]) = rk[i];
+        for (int i = 0; i < KH; ++i) *reinterpret_cast<half8*>(&ks[skey * KS + sd0 + 8 * i]) = rk[i];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
+        for (int i = 0; i < D / 8; ++i) {
             half2v pr;
             pr[0] = rv[i >> 3][i & 7];
-            pr[1] = rv[2 + (i >> 3)][i & 7];
+            pr[1] = rv[VH + (i >> 3)][i & 7];
             *reinterpret_cast<half2v*>(&vt[(vd0 + i) * GM_VS + 2 * vkp]) = pr;
         }
         __syncthreads();
@@ -243,8 +321,8 @@ __global__ __launch_bounds__(256) void attn_gqa_mfma(GqaArgs a) {
 #pragma unroll
             for (int e = 0; e < 16; ++e) st[e] = 0.0f;
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const half8 kf = *reinterpret_cast<const half8*>(&ks[(sub * 32 + c) * GM_KS + 16 * s + 8 * hh]);
+            for (int s = 0; s < NS; ++s) {
+                const half8 kf = *reinterpret_cast<const half8*>(&ks[(sub * 32 + c) * KS + 16 * s + 8 * hh]);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], st, 0, 0, 0);
             }
             // masks only where they can bite (wave-uniform test): the ragged end, the diagonal, the left padding
@@ -266,7 +344,7 @@ __global__ __launch_bounds__(256) void attn_gqa_mfma(GqaArgs a) {
                 l_run *= alpha;
                 m_run = m_new;
 #pragma unroll
-                for (int dt = 0; dt < 4; ++dt)
+                for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                     for (int e = 0; e < 16; ++e) ot[dt][e] *= alpha;
             }
@@ -279,7 +357,7 @@ __global__ __launch_bounds__(256) void attn_gqa_mfma(GqaArgs a) {
                 pf[e >> 3][e & 7] = (_Float16)p;
             }
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
+            for (int dt = 0; dt < NDT; ++dt) {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     const _Float16* vrow = &vt[(dt * 32 + c) * GM_VS];
@@ -294,30 +372,31 @@ __global__ __launch_bounds__(256) void attn_gqa_mfma(GqaArgs a) {
             }
         }
     }
-    // O^T (dims in registers, query on the lane) -> this wave's slice of the (now idle) LDS -> whole 256-byte rows
+    // O^T (dims in registers, query on the lane) -> this wave's slice of the (now idle) LDS -> whole 2 D-byte rows
     l_run += __shfl_xor(l_run, 32, 64);
     const bool qvalid = a.pos0 + q0 + c < len;                        // a padded query (right padding) produces zeros
     const float inv = (qvalid && l_run > 0.0f) ? 1.0f / l_run : 0.0f;
     __syncthreads();                                                  // every wave is done with the K / V^T images
-    _Float16* so = smem + wid * 32 * GM_OS;
+    _Float16* so = smem + wid * 32 * OS;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
+    for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             half4 o4;
 #pragma unroll
             for (int i = 0; i < 4; ++i) o4[i] = (_Float16)(ot[dt][4 * g + i] * inv);
-            *reinterpret_cast<half4*>(&so[c * GM_OS + dt * 32 + 8 * g + 4 * hh]) = o4;
+            *reinterpret_cast<half4*>(&so[c * OS + dt * 32 + 8 * g + 4 * hh]) = o4;
         }
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
+    constexpr int LPR = D / 8;       // lanes (16-byte pieces) per output row
 #pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        const int r = it * 4 + (lane >> 4), col = (lane & 15) * 8;
+    for (int it = 0; it < LPR / 2; ++it) {
+        const int r = it * (64 / LPR) + lane / LPR, col = (lane % LPR) * 8;
         const int qi = q0 + r;
         if (qi < a.tq)
-            *reinterpret_cast<half8*>(a.out + (int64_t)b * a.sob + (int64_t)qi * a.sot + head * GA_D + col) =
-                *reinterpret_cast<const half8*>(&so[r * GM_OS + col]);
+            *reinterpret_cast<half8*>(a.out + (int64_t)b * a.sob + (int64_t)qi * a.sot + head * D + col) =
+                *reinterpret_cast<const half8*>(&so[r * OS + col]);
     }
 }
 
@@ -436,11 +515,12 @@ int astts_op_attn_causal_gqa(const void* q_f16, const void* k_f16, const void* v
                              int32_t t, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
                              astts_stream_t stream) {
     ASTTS_REQUIRE(q_f16 && k_f16 && v_f16 && out_f16, ASTTS_ERR_INVALID, "astts_op_attn_causal_gqa: null pointer");
-    ASTTS_REQUIRE(head_dim == GA_D, ASTTS_ERR_UNSUPPORTED, "astts_op_attn_causal_gqa: head_dim=%d (built for 128; 64 is astts_op_attn_mha)", head_dim);
+    ASTTS_REQUIRE(head_dim == 64 || head_dim == 128, ASTTS_ERR_UNSUPPORTED, "astts_op_attn_causal_gqa: head_dim=%d (built for 64 and 128)", head_dim);
     ASTTS_REQUIRE(b >= 1 && t >= 1 && heads >= 1 && kv_heads >= 1 && heads % kv_heads == 0 && (ldq & 7) == 0 && (ldk & 7) == 0 && (ldo & 7) == 0 &&
                       ((uintptr_t)q_f16 & 15) == 0 && ((uintptr_t)k_f16 & 15) == 0 && ((uintptr_t)v_f16 & 15) == 0 && ((uintptr_t)out_f16 & 15) == 0,
                   ASTTS_ERR_INVALID, "astts_op_attn_causal_gqa: bad shape / alignment b=%d t=%d heads=%d kv_heads=%d", b, t, heads, kv_heads);
-    hipLaunchKernelGGL(attn_causal_gqa, dim3((unsigned)cdiv(t, GA_Q), heads, b), dim3(256), 0, (hipStream_t)stream, (const _Float16*)q_f16,
+    const auto kern = head_dim == GA_D64 ? attn_causal_gqa64 : attn_causal_gqa;
+    hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(t, GA_Q), heads, b), dim3(256), 0, (hipStream_t)stream, (const _Float16*)q_f16,
                        (const _Float16*)k_f16, (const _Float16*)v_f16, lens, (_Float16*)out_f16, t, heads, kv_heads, ldq, ldk, ldo, scale);
     ASTTS_CHECK_LAUNCH();
     return ASTTS_OK;
@@ -450,7 +530,7 @@ int astts_op_attn_gqa(const void* q_f16, const void* k_f16, const void* v_f16, c
                       int32_t b, int32_t tq, int32_t tk, int32_t pos0, int32_t heads, int32_t kv_heads, int32_t head_dim, int64_t sqb, int64_t sqt,
                       int64_t skb, int64_t skt, int64_t sob, int64_t sot, float scale, astts_stream_t stream) {
     ASTTS_REQUIRE(q_f16 && k_f16 && v_f16 && out_f16, ASTTS_ERR_INVALID, "astts_op_attn_gqa: null pointer");
-    ASTTS_REQUIRE(head_dim == GA_D, ASTTS_ERR_UNSUPPORTED, "astts_op_attn_gqa: head_dim=%d (built for 128; 64 is astts_op_attn_mha)", head_dim);
+    ASTTS_REQUIRE(head_dim == 64 || head_dim == 128, ASTTS_ERR_UNSUPPORTED, "astts_op_attn_gqa: head_dim=%d (built for 64 and 128)", head_dim);
     ASTTS_REQUIRE(b >= 1 && tq >= 1 && tk >= 1 && pos0 >= 0 && pos0 + tq <= tk && heads >= 1 && kv_heads >= 1 && heads % kv_heads == 0, ASTTS_ERR_INVALID,
                   "astts_op_attn_gqa: bad shape b=%d tq=%d tk=%d pos0=%d heads=%d kv_heads=%d", b, tq, tk, pos0, heads, kv_heads);
     ASTTS_REQUIRE(((sqb | sqt | skb | skt | sob | sot) & 7) == 0 && ((uintptr_t)q_f16 & 15) == 0 && ((uintptr_t)k_f16 & 15) == 0 &&
@@ -458,7 +538,8 @@ int astts_op_attn_gqa(const void* q_f16, const void* k_f16, const void* v_f16, c
                   ASTTS_ERR_INVALID, "astts_op_attn_gqa: strides must be multiples of 8 halfs and pointers 16-byte aligned");
     GqaArgs a{(const _Float16*)q_f16, (const _Float16*)k_f16, (const _Float16*)v_f16, lens, key_start, (_Float16*)out_f16,
               sqb, sqt, skb, skt, sob, sot, tq, tk, pos0, heads, kv_heads, scale};
-    hipLaunchKernelGGL(attn_gqa_mfma, dim3((unsigned)cdiv(tq, 128), heads, b), dim3(256), 0, (hipStream_t)stream, a);
+    const auto kern = head_dim == 64 ? attn_gqa_mfma<64> : attn_gqa_mfma<128>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)cdiv(tq, 128), heads, b), dim3(256), 0, (hipStream_t)stream, a);
     ASTTS_CHECK_LAUNCH();
     return ASTTS_OK;
 }

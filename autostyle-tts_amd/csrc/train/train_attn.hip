@@ -1,4 +1,4 @@
-// train_attn.hip -- libastts_train.so: causal grouped-query attention backward at head_dim 128 on the matrix cores.
+// train_attn.hip -- libastts_train.so: causal grouped-query attention backward at head_dim 128 or 64 on the matrix cores.
 //
 // Forward (csrc/ops_llm.hip attn_gqa_mfma): S = scale Q K^T (causal, keys < len), P = softmax(S), O = P V.  Backward, per (row, head):
 //   dV = P^T dO      dP = dO V^T      D_i = sum_j P_ij dP_ij      dS = P o (dP - D)      dQ = scale dS K      dK = scale dS^T Q
@@ -10,13 +10,14 @@
 //                 tiles from the diagonal on: dV^T += dO^T P, dK^T += Q^T dS, summed over the group in head order.
 // Every product is v_mfma_f32_32x32x16_f16.  The tile that becomes the next product's B operand (P, dS) is taken straight from the
 // accumulator registers, whose element order fixes the K order of that product (train_common.h); the matching A operand is read from a
-// transposed LDS image.  q is scaled by scale * log2(e) and rounded to fp16 before S, exactly as the forward does, so P is the forward's.
+// transposed LDS image.  The kernels are templates on the head dimension D: S and dP take D / 16 k-steps, the dQ^T / dK^T / dV^T
+// accumulators are D / 32 dimension tiles, a row-major LDS row is D + 8 halfs.  q is scaled by scale * log2(e) and rounded to fp16
+// before S, exactly as the forward does, so P is the forward's.
 #include "train_common.h"
 
 namespace astts_train {
 
-static constexpr int AD = 128;      // head dimension
-static constexpr int RS = 136;      // halfs per row of a row-major LDS tile (128 + 8: 16-byte reads of 32 rows spread over the banks)
+// halfs per row of a row-major LDS tile are D + 8 (136 / 72: 16-byte reads of 32 rows spread over the banks)
 static constexpr int TS = 40;       // halfs per row of a transposed LDS tile (32 + 8)
 static constexpr float LOG2E = 1.44269504088896341f;
 
@@ -50,36 +51,39 @@ __device__ __forceinline__ half8 frag_t(const _Float16* img, int row, int s, int
     return f;
 }
 
-// 32 rows x 128 halfs from global memory (row index clamped to t - 1) into a row-major image (scaled by `mul` when SCALE) and / or a
-// transposed one.  256 threads: thread -> (row = tid >> 3, 16 dims from (tid & 7) * 16)
-template <bool SCALE>
+// 32 rows x D halfs from global memory (row index clamped to t - 1) into a row-major image (scaled by `mul` when SCALE) and / or a
+// transposed one.  256 threads: thread -> (row = tid >> 3, D / 8 dims from (tid & 7) * (D / 8))
+template <int D, bool SCALE>
 __device__ __forceinline__ void stage_tile(const _Float16* src, int64_t ld, int row0, int t, _Float16* rowimg, _Float16* timg, float mul) {
-    const int r = threadIdx.x >> 3, d0 = (threadIdx.x & 7) * 16;
+    constexpr int RS = D + 8, NH = D / 64;
+    const int r = threadIdx.x >> 3, d0 = (threadIdx.x & 7) * (D / 8);
     const _Float16* p = src + (int64_t)min(row0 + r, t - 1) * ld + d0;
-    const half8 a = *reinterpret_cast<const half8*>(p);
-    const half8 b = *reinterpret_cast<const half8*>(p + 8);
+    half8 x[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) x[h] = *reinterpret_cast<const half8*>(p + 8 * h);
     if (timg) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            timg[(d0 + i) * TS + r] = a[i];
-            timg[(d0 + 8 + i) * TS + r] = b[i];
+#pragma unroll
+            for (int h = 0; h < NH; ++h) timg[(d0 + 8 * h + i) * TS + r] = x[h][i];
         }
     }
     if (rowimg) {
-        half8 a2 = a, b2 = b;
-        if (SCALE) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                a2[i] = (_Float16)((float)a[i] * mul);
-                b2[i] = (_Float16)((float)b[i] * mul);
+        for (int h = 0; h < NH; ++h) {
+            half8 x2 = x[h];
+            if (SCALE) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) x2[i] = (_Float16)((float)x[h][i] * mul);
             }
+            *reinterpret_cast<half8*>(&rowimg[r * RS + d0 + 8 * h]) = x2;
         }
-        *reinterpret_cast<half8*>(&rowimg[r * RS + d0]) = a2;
-        *reinterpret_cast<half8*>(&rowimg[r * RS + d0 + 8]) = b2;
     }
 }
 
+template <int AD>
 __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
+    constexpr int RS = AD + 8, NS = AD / 16, NDT = AD / 32;
     __shared__ __attribute__((aligned(16))) _Float16 ks[32 * RS];
     __shared__ __attribute__((aligned(16))) _Float16 vs[32 * RS];
     __shared__ __attribute__((aligned(16))) _Float16 kt[AD * TS];
@@ -98,14 +102,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
     const bool wave_on = q0 < a.t;                                    // wave-uniform
 
     // B operands with the QUERY on the lane: Q (scaled as the forward scales it) and dO
-    half8 qf[8], dof[8];
+    half8 qf[NS], dof[NS];
     {
         const int qr = min(qi, a.t - 1);
         const _Float16* qrow = base + (int64_t)qr * a.ldq + head * AD;
         const _Float16* drow = a.dout + ((int64_t)b * a.t + qr) * a.ldo + head * AD;
         const float sc = a.scale * LOG2E;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
+        for (int s = 0; s < NS; ++s) {
             const half8 x = *reinterpret_cast<const half8*>(qrow + 16 * s + 8 * hh);
 #pragma unroll
             for (int i = 0; i < 8; ++i) qf[s][i] = (_Float16)((float)x[i] * sc);
@@ -118,7 +122,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
         st = zero16();
         dp = zero16();
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
+        for (int s = 0; s < NS; ++s) {
             const half8 kf = *reinterpret_cast<const half8*>(&ks[c * RS + 16 * s + 8 * hh]);
             const half8 vf = *reinterpret_cast<const half8*>(&vs[c * RS + 16 * s + 8 * hh]);
             st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[s], st, 0, 0, 0);
@@ -130,8 +134,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
     float m_run = -INFINITY, l_run = 0.0f, acc = 0.0f;
     for (int j0 = 0; j0 < kend; j0 += 32) {
         __syncthreads();
-        stage_tile<false>(kp, a.ldq, j0, a.t, ks, nullptr, 1.0f);
-        stage_tile<false>(vp, a.ldq, j0, a.t, vs, nullptr, 1.0f);
+        stage_tile<AD, false>(kp, a.ldq, j0, a.t, ks, nullptr, 1.0f);
+        stage_tile<AD, false>(vp, a.ldq, j0, a.t, vs, nullptr, 1.0f);
         __syncthreads();
         if (!wave_on || j0 > q0 + 31) continue;                       // wave-uniform: beyond this wave's last query
         float16v st, dp;
@@ -169,13 +173,13 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
     }
 
     // ---- pass 2: dQ^T[dim][query] += K^T[dim][key] dS^T[key][query]
-    float16v ot[4];
+    float16v ot[NDT];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) ot[dt] = zero16();
+    for (int dt = 0; dt < NDT; ++dt) ot[dt] = zero16();
     for (int j0 = 0; j0 < kend; j0 += 32) {
         __syncthreads();
-        stage_tile<false>(kp, a.ldq, j0, a.t, ks, kt, 1.0f);
-        stage_tile<false>(vp, a.ldq, j0, a.t, vs, nullptr, 1.0f);
+        stage_tile<AD, false>(kp, a.ldq, j0, a.t, ks, kt, 1.0f);
+        stage_tile<AD, false>(vp, a.ldq, j0, a.t, vs, nullptr, 1.0f);
         __syncthreads();
         if (!wave_on || j0 > q0 + 31) continue;
         float16v st, dp;
@@ -189,14 +193,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
             dsf[e >> 3][e & 7] = (_Float16)(p * (dp[e] - dq_sum));
         }
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int s = 0; s < 2; ++s) ot[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag_t(kt, dt * 32 + c, s, hh), dsf[s], ot[dt], 0, 0, 0);
     }
     if (qi < a.t) {
         _Float16* orow = a.dqkv + ((int64_t)b * a.t + qi) * a.ldg + head * AD;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 half4 o4;
@@ -207,7 +211,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq(AttnBwdArgs a) {
     }
 }
 
+template <int AD>
 __global__ __launch_bounds__(256) void attn_bwd_dkdv(AttnBwdArgs a) {
+    constexpr int RS = AD + 8, NS = AD / 16, NDT = AD / 32;
     __shared__ __attribute__((aligned(16))) _Float16 qs[32 * RS];     // Q rows, scaled as the forward scales them
     __shared__ __attribute__((aligned(16))) _Float16 dos[32 * RS];    // dO rows
     __shared__ __attribute__((aligned(16))) _Float16 qt[AD * TS];     // Q^T (unscaled)
@@ -225,19 +231,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(AttnBwdArgs a) {
     const bool wave_on = k0 < len;                                    // wave-uniform: some key of this wave is real
 
     // B operands with the KEY on the lane: K and V
-    half8 kf[8], vf[8];
+    half8 kf[NS], vf[NS];
     {
         const _Float16* krow = base + (int64_t)min(key, a.t - 1) * a.ldq + hq + kvh * AD;
         const _Float16* vrow = krow + hk;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
+        for (int s = 0; s < NS; ++s) {
             kf[s] = *reinterpret_cast<const half8*>(krow + 16 * s + 8 * hh);
             vf[s] = *reinterpret_cast<const half8*>(vrow + 16 * s + 8 * hh);
         }
     }
-    float16v dvt[4], dkt[4];
+    float16v dvt[NDT], dkt[NDT];
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < NDT; ++dt) {
         dvt[dt] = zero16();
         dkt[dt] = zero16();
     }
@@ -249,8 +255,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(AttnBwdArgs a) {
         const float* dsp = a.dsum + ((int64_t)b * a.heads + head) * a.t;
         for (int t0 = kblk; t0 < len; t0 += 32) {                     // causal: queries from the block's first key on
             __syncthreads();
-            stage_tile<true>(qp, a.ldq, t0, a.t, qs, qt, a.scale * LOG2E);
-            stage_tile<false>(dop, a.ldo, t0, a.t, dos, dot_t, 1.0f);
+            stage_tile<AD, true>(qp, a.ldq, t0, a.t, qs, qt, a.scale * LOG2E);
+            stage_tile<AD, false>(dop, a.ldo, t0, a.t, dos, dot_t, 1.0f);
             if (tid < 32) {
                 const int q = min(t0 + tid, a.t - 1);
                 slse[tid] = lsep[q];
@@ -261,7 +267,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(AttnBwdArgs a) {
             // S and dP: element e of lane (c, hh) = (query t0 + mfma_row(e, hh), key k0 + c)
             float16v st = zero16(), dp = zero16();
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
+            for (int s = 0; s < NS; ++s) {
                 const half8 qa = *reinterpret_cast<const half8*>(&qs[c * RS + 16 * s + 8 * hh]);
                 const half8 da = *reinterpret_cast<const half8*>(&dos[c * RS + 16 * s + 8 * hh]);
                 st = __builtin_amdgcn_mfma_f32_32x32x16_f16(qa, kf[s], st, 0, 0, 0);
@@ -277,7 +283,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(AttnBwdArgs a) {
                 dsf[e >> 3][e & 7] = (_Float16)(p * (dp[e] - sdsum[r]));
             }
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
+            for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
                     dvt[dt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(frag_t(dot_t, dt * 32 + c, s, hh), pf[s], dvt[dt], 0, 0, 0);
@@ -289,7 +295,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkdv(AttnBwdArgs a) {
         _Float16* krow = a.dqkv + ((int64_t)b * a.t + key) * a.ldg + hq + kvh * AD;
         _Float16* vrow = krow + hk;
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt)
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 half4 k4, v4;
@@ -319,7 +325,8 @@ int astts_train_attn_gqa_bwd(const void* qkv_f16, const void* dout_f16, const in
                              int32_t heads, int32_t kv_heads, int32_t head_dim, int64_t ld_qkv, int64_t ld_dout, int64_t ld_dqkv,
                              float scale, void* workspace, size_t workspace_bytes, astts_stream_t stream) {
     TRAIN_REQUIRE(qkv_f16 && dout_f16 && dqkv_f16 && b > 0 && t > 0, ASTTS_ERR_INVALID, "attn_gqa_bwd: null pointer or empty batch");
-    TRAIN_REQUIRE(head_dim == AD, ASTTS_ERR_UNSUPPORTED, "attn_gqa_bwd: head_dim %d (built for 128)", head_dim);
+    TRAIN_REQUIRE(head_dim == 64 || head_dim == 128, ASTTS_ERR_UNSUPPORTED, "attn_gqa_bwd: head_dim %d (built for 64 and 128)", head_dim);
+    const int AD = head_dim;
     TRAIN_REQUIRE(heads > 0 && kv_heads > 0 && heads % kv_heads == 0, ASTTS_ERR_INVALID, "attn_gqa_bwd: %d heads over %d kv heads", heads, kv_heads);
     const int64_t width = (int64_t)(heads + 2 * kv_heads) * AD;
     TRAIN_REQUIRE(ld_qkv >= width && ld_dqkv >= width && ld_dout >= (int64_t)heads * AD && ld_qkv % 8 == 0 && ld_dqkv % 8 == 0 && ld_dout % 8 == 0,
@@ -341,9 +348,9 @@ int astts_train_attn_gqa_bwd(const void* qkv_f16, const void* dout_f16, const in
     a.t = t; a.heads = heads; a.kv_heads = kv_heads;
     a.scale = scale;
     const unsigned tiles = (unsigned)cdiv(t, 128);
-    hipLaunchKernelGGL(attn_bwd_dq, dim3(tiles, heads, b), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(head_dim == 64 ? attn_bwd_dq<64> : attn_bwd_dq<128>, dim3(tiles, heads, b), dim3(256), 0, (hipStream_t)stream, a);
     TRAIN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(attn_bwd_dkdv, dim3(tiles, kv_heads, b), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(head_dim == 64 ? attn_bwd_dkdv<64> : attn_bwd_dkdv<128>, dim3(tiles, kv_heads, b), dim3(256), 0, (hipStream_t)stream, a);
     TRAIN_CHECK_LAUNCH();
     return ASTTS_OK;
 }

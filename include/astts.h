@@ -444,15 +444,16 @@ int astts_op_rmsnorm(const float* x, const float* w, void* y, int32_t out_f16, i
  * [>= pos0 + t, head_dim / 2] (llama3-scaled frequencies, built by the host exactly as transformers does) */
 int astts_op_rope_llama(void* x_f16, const float* cos_tab, const float* sin_tab, int32_t b, int32_t t, int32_t heads, int32_t ld,
                         int32_t head_dim, int32_t pos0, astts_stream_t stream);
-/* causal grouped-query attention, head_dim 128: q [b, t, heads*128], k / v [b, t, kv_heads*128] fp16 strided views
- * (row strides ldq / ldk in halfs), lens int32 [b] valid tokens (right padding) or NULL, out fp16 [b, t, ldo] */
+/* causal grouped-query attention, head_dim 64 or 128 (any other value: ASTTS_ERR_UNSUPPORTED): q [b, t, heads*head_dim],
+ * k / v [b, t, kv_heads*head_dim] fp16 strided views (row strides ldq / ldk in halfs), lens int32 [b] valid tokens (right padding)
+ * or NULL, out fp16 [b, t, ldo] */
 int astts_op_attn_causal_gqa(const void* q_f16, const void* k_f16, const void* v_f16, const int32_t* lens, void* out_f16, int32_t b,
                              int32_t t, int32_t heads, int32_t kv_heads, int32_t head_dim, int32_t ldq, int32_t ldk, int32_t ldo, float scale,
                              astts_stream_t stream);
 /* the same attention on the matrix cores (v_mfma_f32_32x32x16_f16; round 5), generalised for the generation path of
  * /root/reference/milvus/search_json.py:178-188 (model.generate, greedy): explicit element strides of batch row / time step
  * (sqb, sqt: q; skb, skt: k and v; sob, sot: out) so that a time-major KV cache is read in place; query i has key index
- * pos0 + i and attends keys [key_start[b], min(pos0 + i + 1, lens[b])) (either mask array may be NULL); head_dim 128 */
+ * pos0 + i and attends keys [key_start[b], min(pos0 + i + 1, lens[b])) (either mask array may be NULL); head_dim 64 or 128 (any other value: ASTTS_ERR_UNSUPPORTED) */
 int astts_op_attn_gqa(const void* q_f16, const void* k_f16, const void* v_f16, const int32_t* lens, const int32_t* key_start, void* out_f16,
                       int32_t b, int32_t tq, int32_t tk, int32_t pos0, int32_t heads, int32_t kv_heads, int32_t head_dim, int64_t sqb, int64_t sqt,
                       int64_t skb, int64_t skt, int64_t sob, int64_t sot, float scale, astts_stream_t stream);

@@ -22,11 +22,11 @@ extern "C" {
 int32_t astts_train_abi_version(void);
 const char* astts_train_last_error_string(void);
 
-/* Causal grouped-query attention backward, head_dim 128, batch-major rows [b, t].
- * qkv: fp16 [b * t, ld_qkv] = q (heads * 128, RoPE applied) | k (kv_heads * 128, RoPE applied) | v (kv_heads * 128);
- * dout: fp16 [b * t, ld_dout], the gradient of the attention output (heads * 128 columns); lens: int32 [b] or NULL (right padding:
+/* Causal grouped-query attention backward, head_dim d = 64 or 128 (any other value: ASTTS_ERR_UNSUPPORTED), batch-major rows [b, t].
+ * qkv: fp16 [b * t, ld_qkv] = q (heads * d, RoPE applied) | k (kv_heads * d, RoPE applied) | v (kv_heads * d);
+ * dout: fp16 [b * t, ld_dout], the gradient of the attention output (heads * d columns); lens: int32 [b] or NULL (right padding:
  * keys at or beyond are masked, queries at or beyond take and give no gradient); dqkv: fp16 [b * t, ld_dqkv] = dq | dk | dv, every
- * row of it written (zeros in the padding).  scale: 1 / sqrt(128).  The softmax statistics are recomputed: the workspace holds
+ * row of it written (zeros in the padding).  scale: 1 / sqrt(d).  The softmax statistics are recomputed: the workspace holds
  * the log-sum-exp and sum_j P_ij dP_ij of every (row, head, query).  All products (S, dP twice; dQ, dK, dV once) are
  * v_mfma_f32_32x32x16_f16 with fp32 accumulation; P and dS are rounded to fp16 where they become MFMA operands. */
 size_t astts_train_attn_gqa_bwd_workspace_bytes(int32_t b, int32_t t, int32_t heads);
