@@ -65,8 +65,11 @@ def test_ring_gemm_bench_shapes_every_tile(shape, mode):
     assert y.dtype == (torch.float16 if o16 else torch.float32)
 
 
-@pytest.mark.parametrize("shape", [(256, 64, 256), (300, 192, 260), (5000, 1024, 4097), (8192, 2048, 2048), (256, 6144, 20000), (40000, 256, 1536)],
-                         ids=lambda s: "x".join(map(str, s)))
+# (rows, k, n) of the eight-phase test below
+EIGHT_PHASE_SHAPES = [(256, 64, 256), (300, 192, 260), (5000, 1024, 4097), (8192, 2048, 2048), (256, 6144, 20000), (40000, 256, 1536)]
+
+
+@pytest.mark.parametrize("shape", EIGHT_PHASE_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_eight_phase_ring_is_bit_identical_to_the_one_barrier_ring(shape):
     """gemm_ring8 (the launcher's 256 x 256 tile from round 6; forced: ring mode 5) multiplies the same tile with the same accumulation
     order per accumulator as gemm_ring<4, 2, 2, 4, 8> (forced: mode 4), so their outputs are equal bit for bit; its LDS-DMA data is ordered
@@ -94,6 +97,45 @@ def test_eight_phase_ring_is_bit_identical_to_the_one_barrier_ring(shape):
                 assert float((y5[rows.to(DEV)].double().cpu() - ref).abs().max() / ref.abs().max()) < 2e-5
     finally:
         ops.set_gemm_ring_mode(-1)
+
+
+# (m, n, K) and the ring switch of the tile the rule gives it: the smallest ragged shapes that reach each branch of the rule
+RULE_BRANCH_SHAPES = [((8190, 515, 1024), 1), ((1279, 1020, 64), 2), ((70, 100, 192), 3), ((3581, 4090, 1024), 5)]
+
+
+@pytest.mark.parametrize("shape,mode", RULE_BRANCH_SHAPES,
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else f"mode{v}")
+def test_automatic_rule_launches_the_tile_the_recorded_plan_names(shape, mode):
+    """The smallest ragged (m, n, K) that reach each branch of the ring rule: the output under the automatic rule equals, bit for bit, the
+    output with the tile forced that tests/golden/gemm_plan.txt records for the shape (the file tests/test_gemm_plan_cpu.py holds
+    csrc/gemm_plan.h to, read here through the same reader, so the two cannot drift).  This is the one place where the GPU confirms that
+    the launcher launches what the plan says, and it is INDIRECT: it shows equality with the named tile's output, not the kernel's name.
+    Both outputs also meet this file's fp32-reference tolerance on sampled rows."""
+    import gemm_plan_golden as gpg
+    from astts import ops
+
+    m, n, k = shape
+    assert gpg.MODE_OF_TILE[gpg.ring_tile(m, n, k)] == mode
+    g = torch.Generator().manual_seed(m * 7 + n)
+    w, b = torch.randn(n, k, generator=g) / math.sqrt(k), torch.randn(n, generator=g)
+    x = torch.randn(m, k, generator=g).half()
+    pw = ops.PackedWeight(w, b)
+    xd = x.to(DEV)
+    assert ops.gemm_kernel_kind(m, n, k, x_f16=True) == "ring"
+    try:
+        ops.set_gemm_ring_mode(-1)
+        y_auto = ops.gemm(xd, pw, out=torch.empty((m, n), dtype=torch.float32, device=DEV))
+        ops.set_gemm_ring_mode(mode)
+        y_tile = ops.gemm(xd, pw, out=torch.empty((m, n), dtype=torch.float32, device=DEV))
+        torch.cuda.synchronize()
+    finally:
+        ops.set_gemm_ring_mode(-1)
+    assert torch.equal(y_auto, y_tile), f"{int((y_auto != y_tile).sum())} elements differ from the forced tile's"
+    rows = torch.randperm(m, generator=g)[:64]
+    ref = F.linear(x[rows].double(), w.half().double(), b.double())
+    err = float((y_auto[rows.to(DEV)].double().cpu() - ref).abs().max() / ref.abs().max())
+    print(f"rule vs forced mode {mode} {shape}: equal; rel err on {len(rows)} rows {err:.2e} (tol 2.0e-05)")
+    assert err < 2e-5
 
 
 def test_fullshape_estimator_pass_config2_geometry():
