@@ -11,12 +11,27 @@ existed); the reference's own values are ``--lr_scheduler linear`` (scripts/trai
 ``--lora_dropout 0.05`` (its LoraConfig), ``--neftune_noise_alpha 5`` and ``--packing`` at ``--max_seq_len 1024`` (its SFTTrainer:
 trl's ConstantLengthDataset -- conversations concatenated in file order and cut into chunks of exactly max_seq_len tokens that attend
 across conversation boundaries).  An ``--lr_scheduler`` this command does not know is an error, not a silently constant rate.
-What the reference does and this does not (NF4 base, bf16, gradient checkpointing, embedding resize, checkpoint resume, the
-evaluation every 50 steps with load_best_model_at_end, multi-GPU): DESIGN.md section 2.  The base may be a Llama or a Qwen2
-checkpoint directory (src/ft_llm_cn.py's Qwen2.5: q / k / v biases, plain RoPE); its config.json decides.
+What the reference does and this does not (NF4 base, bf16, gradient checkpointing, embedding resize, multi-GPU): DESIGN.md
+section 2.  The base may be a Llama or a Qwen2 checkpoint directory (src/ft_llm_cn.py's Qwen2.5: q / k / v biases, plain RoPE); its
+config.json decides.
 
-Writes ``{output_folder}/{ft_model_id}``: the peft adapter directory (adapter_config.json, adapter_model.safetensors) and
-``train_log.jsonl`` (one line per optimizer step: step, loss, grad_norm, lr, loss_scale, skipped)."""
+Evaluation while training, checkpoints, the best adapter and resume (the reference's TrainingArguments, src/ft_llm.py:263-291) are
+flags that default to OFF as well; the reference's run is ``--eval_steps 50 --save_steps 50 --eval_delay 200 --save_total_limit 1
+--load_best_model_at_end``.  A step s counts every call of the trainer's step(), skipped ones included.  After step s with
+``s % eval_steps == 0 and s >= eval_delay`` the ``valid`` file is evaluated as LLMErcTrainer.evaluation_loop does (10 greedy tokens,
+weighted F1, batch 32) on ``LoraTrainer.eval_model()``: the live adapter merged on the device into a second fp16 weight image.  After
+step s with ``s % save_steps == 0``, ``checkpoint-{s}/`` is written (adapter files, the trainer's state, ``trainer_state.json``) and
+the older ones are rotated by transformers' rule (the best is never deleted; a limit of 1 keeps the best and the newest).  The best
+checkpoint is the first with a strictly greater ``eval_weighted-f1``.  ``--load_best_model_at_end`` (needs save_steps to be a multiple
+of eval_steps) writes that checkpoint's adapter to the output directory and hands it to ``--do_eval_dev`` / ``--do_eval_test``.
+With ``--save_steps``, a run whose output directory holds ``checkpoint-*`` CONTINUES from the newest one, bit for bit as if it had
+not stopped; another recipe or other training data there is an error, not a fresh start.  ``--total_steps`` pins the schedule's
+length when an invocation stops before it (``--max_steps``).
+
+Writes ``{output_folder}/{ft_model_id}``: the peft adapter directory (adapter_config.json, adapter_model.safetensors),
+``train_log.jsonl`` (one line per optimizer step: step, loss, grad_norm, lr, loss_scale, skipped) and, when evaluating,
+``result_eval_step-{s}.json`` (``{"metrics": {"eval_weighted-f1": f}, "detail_pred": [[pred, label, raw], ...]}``) and
+``eval_log.jsonl`` (step, eval_weighted-f1)."""
 from __future__ import annotations
 
 import argparse
@@ -60,6 +75,15 @@ def build_parser():
     p.add_argument("--neftune_noise_alpha", type=float, default=0.0, help="NEFTune noise on the embedding output (the reference: 5)")
     p.add_argument("--packing", action="store_true", default=False,
                    help="concatenate the conversations and train on chunks of exactly --max_seq_len (default 1024) tokens, as the reference does")
+    p.add_argument("--eval_steps", type=int, default=0, help="evaluate on the valid file every N steps (0 = never; the reference: 50)")
+    p.add_argument("--save_steps", type=int, default=0, help="write checkpoint-{step}/ every N steps and resume from the newest one (0 = never; the reference: 50)")
+    p.add_argument("--eval_delay", type=int, default=200, help="no evaluation before this step (the reference: 200)")
+    p.add_argument("--save_total_limit", type=int, default=None, help="keep at most N checkpoints, the best always among them (the reference: 1)")
+    p.add_argument("--load_best_model_at_end", action="store_true", default=False,
+                   help="write the adapter of the checkpoint with the best eval_weighted-f1 instead of the last weights (the reference does)")
+    p.add_argument("--total_steps", type=int, default=None,
+                   help="length of the learning-rate schedule when it is not the number of steps this invocation trains to (a run cut short "
+                        "by --max_steps that a later invocation continues)")
     return p
 
 
@@ -140,11 +164,116 @@ def load_base(args):
     return make_llama_weights(cfg, args.seed), cfg, None, None
 
 
+# ---- evaluation while training, checkpoints, best model, resume: transformers' Trainer rules as the reference's TrainingArguments
+# (src/ft_llm.py:263-291) use them.  A step s is the trainer's sched_step after the step: every call of step(), skipped ones included.
+EVAL_BATCH, EVAL_MAX_LENGTH = 32, 512
+ADAPTER_FILES = ("adapter_config.json", "adapter_model.safetensors")
+TRAINER_STATE = "trainer_state.json"
+
+
+def should_eval(step: int, eval_steps: int, eval_delay: int) -> bool:
+    return eval_steps > 0 and step % eval_steps == 0 and step >= eval_delay
+
+
+def should_save(step: int, save_steps: int) -> bool:
+    return save_steps > 0 and step % save_steps == 0
+
+
+def is_better(metric: float, best) -> bool:
+    """Strictly greater (weighted F1: greater is better); a tie keeps the earlier checkpoint."""
+    return best is None or metric > best
+
+
+def checkpoints_to_delete(steps, best_step, limit):
+    """transformers' Trainer._rotate_checkpoints on the saved steps: sorted by step, the best moved to just before the newest; a
+    limit of 1 becomes 2 while the best is not the newest; what exceeds the limit goes, from the front."""
+    order = sorted(int(s) for s in steps)
+    if limit is None or limit <= 0 or len(order) <= limit:
+        return []
+    if best_step is not None and best_step in order:
+        i = order.index(best_step)
+        for j in range(i, len(order) - 2):
+            order[j], order[j + 1] = order[j + 1], order[j]
+    if best_step is not None and limit == 1 and order[-1] != best_step:
+        limit = 2
+    return order[:max(0, len(order) - limit)]
+
+
+def check_flags(args) -> None:
+    for name in ("eval_steps", "save_steps", "eval_delay"):
+        if getattr(args, name) < 0:
+            raise SystemExit(f"ft_llm: --{name} {getattr(args, name)} is negative")
+    if args.load_best_model_at_end:
+        if args.eval_steps <= 0 or args.save_steps <= 0 or args.save_steps % args.eval_steps != 0:
+            raise SystemExit(f"ft_llm: --load_best_model_at_end needs --save_steps ({args.save_steps}) to be a positive multiple of "
+                             f"--eval_steps ({args.eval_steps}): the best evaluation must have a checkpoint")
+
+
+def data_fingerprint(seqs) -> dict:
+    """The number of training sequences and a SHA-256 of their token ids (each sequence: its length, then its ids, as little-endian int64)."""
+    import hashlib
+    import struct
+    h = hashlib.sha256()
+    for s in seqs:
+        h.update(struct.pack(f"<{len(s) + 1}q", len(s), *s))
+    return {"sequences": len(seqs), "sha256": h.hexdigest()}
+
+
+def data_position_to_json(order, pos: int, rng: random.Random) -> dict:
+    v, internal, gauss = rng.getstate()
+    return {"order": [int(i) for i in order], "pos": int(pos), "random_state": [v, list(internal), gauss]}
+
+
+def data_position_from_json(d: dict):
+    """-> (order, pos, a random.Random that draws what the saved one would have drawn next)."""
+    v, internal, gauss = d["random_state"]
+    rng = random.Random()
+    rng.setstate((v, tuple(int(i) for i in internal), gauss))
+    return [int(i) for i in d["order"]], int(d["pos"]), rng
+
+
+def checkpoint_steps(out_dir: str):
+    out = []
+    for name in os.listdir(out_dir) if os.path.isdir(out_dir) else ():
+        head, _, num = name.partition("-")
+        if head == "checkpoint" and num.isdigit() and os.path.isfile(os.path.join(out_dir, name, TRAINER_STATE)):
+            out.append(int(num))
+    return sorted(out)
+
+
+def _trim_log(path: str, last_step: int) -> None:
+    """Keep the lines of steps <= last_step: a run killed after its last checkpoint logged steps that the resumed run takes again."""
+    if not os.path.exists(path):
+        return
+    with open(path) as f:
+        lines = [ln for ln in f if ln.strip()]
+    keep = [ln for ln in lines if int(json.loads(ln)["step"]) <= last_step]
+    if len(keep) != len(lines):
+        with open(path, "w") as f:
+            f.writelines(keep)
+
+
+def evaluate_in_training(trainer, tokenizer, valid_rows, out_dir: str, step: int) -> float:
+    """The reference's LLMErcTrainer.evaluation_loop on the dev rows at the trainer's CURRENT adapter: 10 greedy tokens per row
+    through ``trainer.eval_model()``, weighted F1, ``result_eval_step-{step}.json`` in its format."""
+    from astts.metrics import weighted_f1
+    emb = trainer.eval_model(tokenizer, EVAL_MAX_LENGTH)
+    label_set = sorted({r["messages"][-1]["content"] for r in valid_rows})
+    recs = evaluate_erc.evaluate_rows(valid_rows, emb, label_set, "generate", EVAL_BATCH, EVAL_MAX_LENGTH, "right")
+    f1 = float(weighted_f1([r["label"] for r in recs], [r["pred"] for r in recs]))
+    with open(os.path.join(out_dir, f"result_eval_step-{step}.json"), "w") as f:
+        json.dump({"metrics": {"eval_weighted-f1": f1}, "detail_pred": [[r["pred"], r["label"], r["raw"]] for r in recs]}, f, indent=1)
+    return f1
+
+
 def train(args, state, cfg, tok, base):
+    import shutil
+
     import torch
 
     from astts.llm.tokenizer import HashTokenizer
     from astts.llm.train import LoraTrainer
+    check_flags(args)
     tokenizer = tok or HashTokenizer(cfg)
     rows = evaluate_erc.read_rows(split_path(args, "train"), args.limit)
     if args.packing:
@@ -153,21 +282,45 @@ def train(args, state, cfg, tok, base):
         seqs = encode_rows(rows, tokenizer, args.max_seq_len)
     if not seqs:
         raise SystemExit(f"ft_llm: no usable rows in {split_path(args, 'train')}")
+    valid_rows = evaluate_erc.read_rows(split_path(args, "valid"), args.limit) if args.eval_steps > 0 else []
     steps, _ = plan_steps(len(seqs), args.epoch, args.max_steps)
+    total_steps = int(args.total_steps) if args.total_steps else steps
     out_dir = os.path.join(args.output_folder, args.ft_model_id or "ft_model")
     os.makedirs(out_dir, exist_ok=True)
     adapter = None
     if args.ft_model_path:
         from astts.llm.peft import load_adapter
         adapter = load_adapter(args.ft_model_path)
-    trainer = LoraTrainer(state, cfg, r=args.lora_r, lora_alpha=LORA_ALPHA, seed=args.seed, adapter=adapter, lr=args.lr, total_steps=steps,
+    trainer = LoraTrainer(state, cfg, r=args.lora_r, lora_alpha=LORA_ALPHA, seed=args.seed, adapter=adapter, lr=args.lr, total_steps=total_steps,
                           loss_scale=args.loss_scale, base_model_name_or_path=base or args.base_model_id,
                           rope_len=max(len(s) for s in seqs) + 64, lora_dropout=args.lora_dropout, neftune_alpha=args.neftune_noise_alpha,
                           schedule=args.lr_scheduler)
     rng = random.Random(args.seed)
     order, pos = [], 0
-    with open(os.path.join(out_dir, "train_log.jsonl"), "w") as log:
-        for _ in range(steps):
+    fingerprint = data_fingerprint(seqs)
+    best_metric, best_ckpt = None, None
+    ckpt_dir = lambda s: os.path.join(out_dir, f"checkpoint-{s}")
+    saved = checkpoint_steps(out_dir) if args.save_steps > 0 else []
+    train_log, eval_log = os.path.join(out_dir, "train_log.jsonl"), os.path.join(out_dir, "eval_log.jsonl")
+    if saved:                                               # resume from the newest checkpoint, as the reference does (src/ft_llm.py:315)
+        with open(os.path.join(ckpt_dir(saved[-1]), TRAINER_STATE)) as f:
+            ts = json.load(f)
+        if ts["data"] != fingerprint:
+            raise SystemExit(f"ft_llm: {ckpt_dir(saved[-1])} was trained on other data ({ts['data']} there, {fingerprint} here); "
+                             "resume needs the same sequences -- use another --ft_model_id for a fresh run")
+        trainer.load_state(ckpt_dir(saved[-1]))             # a recipe that differs: ValueError naming the key
+        if trainer.sched_step != ts["global_step"]:
+            raise SystemExit(f"ft_llm: {ckpt_dir(saved[-1])} is inconsistent: global_step {ts['global_step']}, trainer at {trainer.sched_step}")
+        order, pos, rng = data_position_from_json(ts["data_position"])
+        best_metric, best_ckpt = ts["best_metric"], ts["best_model_checkpoint"]
+        for path in (train_log, eval_log):
+            _trim_log(path, trainer.sched_step)
+        print(f"resuming from {ckpt_dir(saved[-1])} (step {trainer.sched_step} of {steps})")
+    else:
+        for path in (train_log, eval_log) if args.eval_steps > 0 else (train_log,):
+            open(path, "w").close()                         # a fresh run starts its logs; a resumed one appends to them
+    with open(train_log, "a") as log:
+        while trainer.sched_step < steps:
             batches = []
             for _ in range(ACCUM):
                 if pos >= len(order):                       # a new epoch: reshuffle
@@ -182,8 +335,33 @@ def train(args, state, cfg, tok, base):
             log.write(json.dumps(rec) + "\n")
             log.flush()
             print(rec)
-    trainer.save_adapter(out_dir)
-    print(f"adapter saved to {out_dir}")
+            s = trainer.sched_step
+            if should_eval(s, args.eval_steps, args.eval_delay):
+                f1 = evaluate_in_training(trainer, tokenizer, valid_rows, out_dir, s)
+                with open(eval_log, "a") as f:
+                    f.write(json.dumps({"step": s, "eval_weighted-f1": f1}) + "\n")
+                print({"step": s, "eval_weighted-f1": f1})
+                if is_better(f1, best_metric) and should_save(s, args.save_steps):
+                    best_metric, best_ckpt = f1, f"checkpoint-{s}"
+            if should_save(s, args.save_steps):
+                trainer.save_adapter(ckpt_dir(s))
+                trainer.save_state(ckpt_dir(s))
+                with open(os.path.join(ckpt_dir(s), TRAINER_STATE), "w") as f:
+                    json.dump({"global_step": s, "best_metric": best_metric, "best_model_checkpoint": best_ckpt, "data": fingerprint,
+                               "data_position": data_position_to_json(order, pos, rng)}, f)
+                best_step = int(best_ckpt.split("-")[1]) if best_ckpt else None
+                for old in checkpoints_to_delete(checkpoint_steps(out_dir), best_step, args.save_total_limit):
+                    shutil.rmtree(ckpt_dir(old))
+    if args.load_best_model_at_end and best_ckpt is not None:
+        from astts.llm.peft import load_adapter
+        best_dir = os.path.join(out_dir, best_ckpt)
+        trainer.set_adapter(load_adapter(best_dir))         # --do_eval_dev / --do_eval_test see the best adapter
+        for name in ADAPTER_FILES:
+            shutil.copyfile(os.path.join(best_dir, name), os.path.join(out_dir, name))
+        print(f"best adapter ({best_ckpt}, eval_weighted-f1 {best_metric}) saved to {out_dir}")
+    else:
+        trainer.save_adapter(out_dir)
+        print(f"adapter saved to {out_dir}")
     torch.cuda.synchronize()
     return trainer, out_dir
 

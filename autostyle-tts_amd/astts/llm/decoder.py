@@ -107,6 +107,25 @@ class LlamaDecoder:
             self._rope_lock = threading.Lock()
             self._rope_tables(rope_len)
 
+    @classmethod
+    def adopt(cls, base: "LlamaDecoder", layers: List[dict], rope_len: int = 0, **kw):
+        """A second fp16 decoder over prepared weights: ``layers`` (one dict per layer with the keys of ``base.L``) are taken as they
+        are, the embedding table, final norm, head and RoPE tables are ``base``'s own tensors.  Nothing is read from a state dict,
+        nothing is packed.  ``kw``: what a subclass adds (LlamaEmbedder: tokenizer, max_length)."""
+        assert not base.int8 and len(layers) == len(base.L) and all(set(l) == set(b) for l, b in zip(layers, base.L))
+        self = cls.__new__(cls)
+        self.cfg, self.device, self.mfma_attention = base.cfg, base.device, base.mfma_attention
+        self.int8, self.int8_threshold = False, base.int8_threshold
+        self.embed, self.norm, self.head, self.L = base.embed, base.norm, base.head, layers
+        self._rope_lock = threading.Lock()
+        self._rope = base._rope
+        self._rope_for(rope_len)                     # longer than the base's tables: this decoder grows a pair of its own
+        self._adopted(**kw)
+        return self
+
+    def _adopted(self) -> None:
+        pass
+
     def _lin(self, x: torch.Tensor, w, seg, residual=None, out_dtype=torch.float32) -> torch.Tensor:
         """One projection: the fp16 GEMM (ops.linear), or with int8 the LLM.int8 + LoRA GEMM on the segments ``seg`` = (ids, count)."""
         if self.int8:

@@ -30,6 +30,11 @@ class LlamaEmbedder(LlamaDecoder):
         self.tokenizer = tokenizer or HashTokenizer(cfg)
         self.max_length = max_length                                  # truncation=True, max_length=512: src/search_milvus.py:92
 
+    def _adopted(self, tokenizer=None, max_length: int = 512) -> None:
+        """LlamaDecoder.adopt's hook: ``LlamaEmbedder.adopt(base, layers, rope_len, tokenizer=..., max_length=...)``."""
+        self.tokenizer = tokenizer or HashTokenizer(self.cfg)
+        self.max_length = max_length
+
     def _is_eos(self, tok: int) -> bool:
         return tok == self.cfg.eos_token_id or tok in self.cfg.eos_token_ids
 

@@ -16,6 +16,10 @@ dropout on its input, so q, k and v mask the same ``h1`` independently; the mask
 (``noise_seed``, layer * 8 + position in PROJ, the forward's ``draw``) that ``lora_down`` regenerates in its operand load,
 ``lora_grad_dropout`` (dA) in its operand load and ``lora_dx_dropout`` in its epilogue.  dB needs nothing: ``t`` carries the mask.
 NEFTune adds ``alpha / sqrt(T * hidden) * U(-1, 1)`` to the embedding output of a training forward.
+
+Evaluation while training: ``eval_model()`` is a LlamaEmbedder on the CURRENT adapter -- ``train_ops.lora_merge`` writes
+``fp16(W + scaling B A)`` from the fp32 masters into a second image of every fused projection, on the device.  ``save_state`` /
+``load_state`` carry the masters, Adam's moments, the counters and the recipe; a resumed run equals an uninterrupted one bit for bit.
 """
 from __future__ import annotations
 
@@ -123,7 +127,7 @@ class StepReport:
 
 class _Group:
     """One fused projection's LoRA: masters (views into the trainer's flat buffers) and the packed fp16 operands made from them."""
-    __slots__ = ("name", "parts", "outs", "cin", "a", "ga", "b", "gb", "a_pack", "b_pack", "at_pack", "bt_pack", "bblk", "stream")
+    __slots__ = ("name", "parts", "outs", "cin", "a", "ga", "b", "gb", "a_pack", "b_pack", "at_pack", "bt_pack", "bblk", "stream", "bcat")
 
 
 class LoraTrainer:
@@ -175,13 +179,14 @@ class LoraTrainer:
                     g.a = self.params[off:off + R * g.cin].view(R, g.cin)
                     g.ga = self.grads[off:off + R * g.cin].view(R, g.cin)
                     off += R * g.cin
-                    g.b, g.gb = [], []
+                    g.b, g.gb, b0 = [], [], off
                     for j, p in enumerate(parts):
                         g.a[j * rr:(j + 1) * rr].copy_(self.adapter0.pairs[(i, p)][0])
                         g.b.append(self.params[off:off + g.outs[j] * rr].view(g.outs[j], rr))
                         g.gb.append(self.grads[off:off + g.outs[j] * rr].view(g.outs[j], rr))
                         g.b[-1].copy_(self.adapter0.pairs[(i, p)][1])
                         off += g.outs[j] * rr
+                    g.bcat = self.params[b0:off].view(nout, rr)                        # the parts' B back to back: one [out, r] master
                     g.bblk = torch.zeros(nout, R, dtype=torch.float32, device=dev)
                     g.a_pack = ops.PackedWeight(g.a, None, dev)                       # [R, in]:    t = x A^T
                     g.b_pack = ops.PackedWeight(g.bblk, None, dev)                    # [out, R]:   y += t (scaling B)^T
@@ -196,6 +201,7 @@ class LoraTrainer:
             head = state["model.embed_tokens.weight"] if cfg.tie_embeddings else state["lm_head.weight"]
             self.headT = ops.PackedWeight(head.to(dev).t().contiguous(), None, dev)
             self.nsq = torch.zeros(1, dtype=torch.float32, device=dev)
+            self._eval = None           # eval_model()'s embedder: built on first use
             self.repack()
 
     # ------------------------------------------------------------------------------------------------ parameters
@@ -243,6 +249,87 @@ class LoraTrainer:
 
     def save_adapter(self, path: str) -> None:
         save_adapter(self.adapter(), path, self.lora_dropout)
+
+    def set_adapter(self, adapter: LoraAdapter) -> None:
+        """The masters <- ``adapter``'s pairs (same r, every projection); the optimizer state stays.  Repacks."""
+        rr = self.r
+        if adapter.r != rr:
+            raise ValueError(f"set_adapter: r {adapter.r} where the trainer has {rr}")
+        for i, gl in enumerate(self.G):
+            for g in gl.values():
+                for j, p in enumerate(g.parts):
+                    a, b = adapter.pairs[(i, p)]
+                    g.a[j * rr:(j + 1) * rr].copy_(a)
+                    g.b[j].copy_(b)
+        self.repack()
+
+    # ------------------------------------------------------------------------------------------------ evaluation while training
+    def eval_model(self, tokenizer=None, max_length: int = 512):
+        """A LlamaEmbedder that computes with the CURRENT adapter merged into the base: the inference path (generation, scoring) at
+        plain fp16 speed.  Built on first use from ``self.dec`` -- it shares the embedding table, norms, head, biases and RoPE tables
+        and owns a second fp16 image of the four fused projections per layer; EVERY call refreshes those images from the fp32 masters
+        with ``train_ops.lora_merge`` (a device kernel; nothing goes through the host, the images are not reallocated).  The frozen
+        base and the training state are not touched: no draw is taken."""
+        from ..ops import PackedWeight
+        from .embedder import LlamaEmbedder
+        if self._eval is None:
+            with torch.cuda.device(self.device):
+                layers = [{k: (PackedWeight.zeros_like(v) if k in dict(GROUPS) else v) for k, v in L.items()} for L in self.dec.L]
+                self._eval = LlamaEmbedder.adopt(self.dec, layers, rope_len=max(max_length, 16) + 64, tokenizer=tokenizer, max_length=max_length)
+        emb = self._eval
+        if tokenizer is not None:
+            emb.tokenizer = tokenizer
+        emb.max_length = max_length
+        with torch.cuda.device(self.device):
+            for L, E, gl in zip(self.dec.L, emb.L, self.G):
+                for name, g in gl.items():
+                    n = sum(g.outs)
+                    g1 = g.outs[0]
+                    g2 = n if len(g.outs) < 3 else g.outs[0] + g.outs[1]
+                    self.tops.lora_merge(L[name], g.a, g.bcat, E[name], self.r, g1, g2, self.scaling)
+        return emb
+
+    # ------------------------------------------------------------------------------------------------ state: save / resume
+    STATE_TENSORS, STATE_JSON = "trainer_state.safetensors", "trainer_recipe.json"
+
+    def recipe(self) -> dict:
+        """What a saved state belongs to: the adapter's and the optimizer's hyper-parameters, the schedule, the noise, the model shape."""
+        import dataclasses
+        return {"r": self.r, "lora_alpha": self.lora_alpha, "lr": self.lr, "schedule": self.schedule, "total_steps": self.total_steps,
+                "warmup_ratio": self.warmup_ratio, "lora_dropout": self.lora_dropout, "neftune_alpha": self.neftune_alpha,
+                "noise_seed": self.noise_seed, "betas": list(self.betas), "eps": self.eps, "weight_decay": self.weight_decay,
+                "max_grad_norm": self.max_grad_norm, "shape": json.loads(json.dumps(dataclasses.asdict(self.cfg)))}
+
+    def save_state(self, path: str) -> None:
+        """Everything the next step depends on besides the frozen base and the data: the fp32 masters, Adam's m and v (safetensors),
+        and the counters ``draw``, ``opt_step``, ``sched_step``, ``loss_scale`` with ``recipe()`` (JSON).  No pickle."""
+        from safetensors.torch import save_file
+        os.makedirs(path, exist_ok=True)
+        save_file({"params": self.params.detach().cpu(), "m": self.m.detach().cpu(), "v": self.v.detach().cpu()},
+                  os.path.join(path, self.STATE_TENSORS), metadata={"format": "pt"})
+        with open(os.path.join(path, self.STATE_JSON), "w") as f:
+            json.dump({"recipe": self.recipe(), "draw": self.draw, "opt_step": self.opt_step, "sched_step": self.sched_step,
+                       "loss_scale": self.loss_scale}, f, indent=2, sort_keys=True)
+
+    def load_state(self, path: str) -> None:
+        """``save_state``'s directory into this trainer.  A recipe that differs from this trainer's in any key is refused (ValueError
+        naming the key): the continued run would not be the run that was saved.  Repacks the fp16 operands."""
+        from safetensors.torch import load_file
+        with open(os.path.join(path, self.STATE_JSON)) as f:
+            st = json.load(f)
+        mine, theirs = self.recipe(), st["recipe"]
+        for k in sorted(set(mine) | set(theirs)):
+            if k not in mine or k not in theirs or mine[k] != theirs[k]:
+                raise ValueError(f"load_state: {path} was saved under another recipe: {k!r} is {theirs.get(k)!r} there and {mine.get(k)!r} here")
+        t = load_file(os.path.join(path, self.STATE_TENSORS))
+        for name, dst in (("params", self.params), ("m", self.m), ("v", self.v)):
+            if t[name].shape != dst.shape or t[name].dtype != torch.float32:
+                raise ValueError(f"load_state: {name} is {tuple(t[name].shape)} {t[name].dtype}, expected {tuple(dst.shape)} float32")
+        for name, dst in (("params", self.params), ("m", self.m), ("v", self.v)):
+            dst.copy_(t[name])
+        self.draw, self.opt_step, self.sched_step = int(st["draw"]), int(st["opt_step"]), int(st["sched_step"])
+        self.loss_scale = float(st["loss_scale"])
+        self.repack()
 
     # ------------------------------------------------------------------------------------------------ forward / backward
     def _drop(self, g: _Group, draw: Optional[int]):

@@ -108,6 +108,15 @@ class PackedWeight:
         self.bias = None if bias is None else bias.to(device=device, dtype=torch.float32).contiguous()
 
     @staticmethod
+    def zeros_like(other: "PackedWeight") -> "PackedWeight":
+        """A zero image of ``other``'s geometry on its device, for a kernel to fill (train_ops.lora_merge).  The bias is SHARED."""
+        pw = PackedWeight.__new__(PackedWeight)
+        pw.n, pw.taps, pw.cin, pw.cin_pad, pw.n_pad = other.n, other.taps, other.cin, other.cin_pad, other.n_pad
+        pw.data = torch.zeros_like(other.data)
+        pw.bias = other.bias
+        return pw
+
+    @staticmethod
     def from_conv1d(weight: torch.Tensor, bias=None, device=None) -> "PackedWeight":
         """torch Conv1d weight ``[cout, cin, k]`` -> taps-major ``[cout, k, cin]``."""
         return PackedWeight(weight.permute(0, 2, 1).contiguous(), bias, device)

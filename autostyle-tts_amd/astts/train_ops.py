@@ -115,6 +115,23 @@ def adamw_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, s
                                  float(eps), float(weight_decay), 1.0 - beta1 ** step, 1.0 - beta2 ** step, float(grad_mul), _st()))
 
 
+def lora_merge(w_pack, a: torch.Tensor, b: torch.Tensor, out_pack, r: int, g1: int, g2: int, scaling: float):
+    """``out_pack`` <- fp16(``w_pack`` + scaling * B A), part by part: ``w_pack`` / ``out_pack`` are PackedWeights of one geometry
+    (distinct images), ``a`` the fp32 master ``[parts * r, cin]``, ``b`` the fp32 master ``[n, r]`` (the parts' B back to back), rows
+    below ``g1`` part 0, below ``g2`` part 1, the rest part 2 (``g1 = g2 = n``: a single projection).  fp32 accumulation in a fixed
+    order: repeatable bit for bit.  ``w_pack`` is left as it is."""
+    n, cin = w_pack.n, w_pack.cin
+    assert w_pack.taps == 1 and out_pack.taps == 1 and (out_pack.n, out_pack.cin, out_pack.n_pad, out_pack.cin_pad) == (n, cin, w_pack.n_pad, w_pack.cin_pad)
+    assert w_pack.data.dtype == out_pack.data.dtype == torch.float16 and w_pack.data.is_contiguous() and out_pack.data.is_contiguous()
+    parts = 1 + (1 if g1 < n else 0) + (1 if g2 < n else 0)
+    for t in (a, b):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == w_pack.data.device, (t.dtype, t.shape, t.device)
+    assert a.shape == (parts * r, cin) and b.shape == (n, r), (a.shape, b.shape, parts, r, n, cin)
+    check(_L().astts_train_lora_merge(w_pack.data.data_ptr(), a.data_ptr(), b.data_ptr(), out_pack.data.data_ptr(), n, cin, w_pack.n_pad,
+                                      w_pack.cin_pad, int(r), int(g1), int(g2), float(scaling), _st()))
+    return out_pack
+
+
 # ---- the regularisers: LoRA dropout from a counter-based generator (no stored masks) and NEFTune.  The contract of (seed, rng_stream,
 # draw) is in include/train/astts_train.h; part j of a fused projection uses rng_stream + j
 NEFTUNE_STREAM = 0xFFFFFFFF

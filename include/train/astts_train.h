@@ -15,8 +15,8 @@
 extern "C" {
 #endif
 
-/* Stays 1: the version counts changes that break a caller.  The regulariser entry points at the end of this header were added under
- * it; every earlier prototype is unchanged. */
+/* Stays 1: the version counts changes that break a caller.  The regulariser entry points and astts_train_lora_merge at the end of this header
+ * were added under it; every earlier prototype is unchanged. */
 #define ASTTS_TRAIN_ABI_VERSION 1
 
 int32_t astts_train_abi_version(void);
@@ -112,6 +112,17 @@ int astts_train_lora_grad_dropout(const void* u, int32_t u_f32, int64_t ldu, con
 int astts_train_lora_dx_dropout(const void* dt_f16, int64_t lddt, const void* at_f16, int64_t ldat, const float* residual, void* dx,
                                 int32_t dx_f16, int64_t rows, int32_t cin, int32_t parts, int32_t r, double p, int64_t seed,
                                 uint32_t rng_stream, uint32_t draw, astts_stream_t stream);
+
+/* ---- Evaluation while training: the live adapter merged into a second weight image (added under ABI 1, as the regularisers were).
+ *   out[o, i] = fp16_rn(float(w[o, i]) + scaling * sum_{k < r} b[o, k] * a[part(o) * r + k, i]),   o < n, i < cin
+ *   part(o)   = (o >= g1) + (o >= g2): the parts of a fused projection (q | k | v, gate | up); g1 = g2 = n for a single one
+ * w, out: fp16 [n_pad, cin_pad] in astts_op_pack_weight's layout (n_pad a multiple of 128, cin_pad of 64); the padding rows and
+ * columns of out are written as zeros.  a: the fp32 master [parts * r, cin]; b: the fp32 master [n, r] (the parts' B matrices back to
+ * back); r a multiple of 8; g1 and g2 multiples of 32 (or n), 0 < g1 <= g2 <= n, equal only at n (two parts: g2 = n).  out may not overlap w: the frozen base survives.
+ * fp32 throughout: one fma chain over k = 0 .. r - 1 per element, one more fma joins the base, one rounding to fp16; no atomics, so
+ * the image is bit-for-bit repeatable. */
+int astts_train_lora_merge(const void* w_f16, const float* a, const float* b, void* out_f16, int32_t n, int32_t cin, int32_t n_pad,
+                           int32_t cin_pad, int32_t r, int32_t g1, int32_t g2, float scaling, astts_stream_t stream);
 
 #ifdef __cplusplus
 }
