@@ -135,7 +135,7 @@ def test_embedding_interp_time():
     assert rel_err(ops.embedding(tab.to(DEV), ids.to(DEV)), tab[ids]) == 0.0
     x = torch.randn(2, 150, 80, generator=g)
     for t_out in (258, 430, 75, 150):
-        ref = F.interpolate(x.transpose(1, 2), size=t_out, mode="linear").transpose(1, 2)
+        ref = F.interpolate(x.double().transpose(1, 2), size=t_out, mode="linear").transpose(1, 2)   # float64: float32 torch is 1.7e-5 off it
         assert rel_err(ops.interp_linear(x.to(DEV), t_out), ref) < 1e-5
     t = torch.tensor([0.0, 0.3, 0.97, 1.0])
     half = 160
