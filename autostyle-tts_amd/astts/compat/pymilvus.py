@@ -10,6 +10,9 @@ Mirrors exactly the calls the reference makes (paths under /root/reference):
                                                             milvus/search_json.py:246-252
   .create_collection(collection_name, dimension) / .insert(collection_name, data=[{...}]) /
   .drop_collection(collection_name)                          milvus/RAG.py:49-57,541-544
+and the calls that maintain a collection after ``insert`` (not made by the reference; pymilvus' names and result keys):
+  .delete(collection_name, ids= | filter=) / .upsert(collection_name, data) / .query(...) / .get(collection_name, ids) /
+  .get_collection_stats(collection_name) / .compact(collection_name)
   FieldSchema / CollectionSchema / DataType, .create_collection(schema=CollectionSchema(...)), .create_index(...)
                                                             milvus/insert_embeddings.py:52-79 (auto_id pk, VARCHAR fields)
 Result shape: ``list[Q]`` of ``list[k]`` of ``{'id': pk, 'distance': cosine_similarity,
@@ -20,12 +23,14 @@ expressions over the primary key and the dynamic fields (astts.milvus_filter) be
 ``limit`` up to 1024 (32 hits per selection pass over one scan).
 
 The file behind ``db_path`` is read with astts.milvus_lite (SQLite + protobuf wire format); the
-vectors go to HBM once per collection and stay there.  Errors raise ``MilvusException`` -- the
+vectors go to HBM once per collection and stay there: ``insert`` appends to the resident bank, ``delete`` / ``upsert`` tombstone its
+rows, ``compact`` squeezes them out (astts.knn.StyleBank.append / delete_rows / compact).  Errors raise ``MilvusException`` -- the
 reference wraps every call in try/except and degrades to ``[]`` itself
 (milvus/search_embeddings.py:24-27), so the shim does not swallow anything.
 
 Extra keys beyond pymilvus: each hit also carries ``'row'`` (row index in the bank == style id,
-because the reference's pk restarts per speaker and is not unique: milvus/RAG.py:507).
+because the reference's pk restarts per speaker and is not unique: milvus/RAG.py:507).  A row keeps its index through inserts and
+deletes; ``compact`` renumbers the rows that are left.
 """
 from __future__ import annotations
 
@@ -89,7 +94,12 @@ class _Collection:
         self.vectors: List[np.ndarray] = []
         self.pks: List[int] = []
         self.metas: List[Dict[str, Any]] = []
-        self._bank = None  # astts.knn.StyleBank, built lazily, dropped on insert
+        self.live: List[bool] = []      # vectors / pks / metas / live are row-aligned with the bank; a deleted row stays until compact
+        self.n_live = 0
+        self._bank = None  # astts.knn.StyleBank, built lazily by the first search, then kept up to date in place
+
+    def live_rows(self) -> List[int]:
+        return [i for i, on in enumerate(self.live) if on]
 
     def matrix(self) -> np.ndarray:
         if not self.vectors:
@@ -104,6 +114,8 @@ class _Collection:
             m16 = m.astype(np.float16)
             # upload as fp16 when that is lossless (half the HBM traffic of every scan)
             self._bank = StyleBank(m16 if np.array_equal(m16.astype(np.float32), m) else m, metric=self.metric)
+            if self.n_live < len(self.live):      # rows deleted before the first search: the bank stays row-aligned with the lists
+                self._bank.delete_rows([i for i, on in enumerate(self.live) if not on])
         return self._bank
 
 
@@ -127,6 +139,8 @@ class MilvusClient:
                     c.vectors = [v[i] for i in range(v.shape[0])]
                     c.pks = [int(x) for x in pks]
                     c.metas = metas
+                    c.live = [True] * len(c.pks)
+                    c.n_live = len(c.pks)
                     self._colls[name] = c
             finally:
                 f.close()
@@ -160,7 +174,7 @@ class MilvusClient:
                 {"field_id": 101, "name": c.vector_field, "description": "", "type": 101, "params": {"dim": c.dim}},
             ],
             "enable_dynamic_field": True,
-            "num_entities": len(c.pks),
+            "num_entities": c.n_live,
             "metric_type": c.metric,
         }
 
@@ -202,30 +216,149 @@ class MilvusClient:
         if self._colls.pop(collection_name, None) is not None and self._file():
             self._file().drop_collection(collection_name)
 
-    def insert(self, collection_name: str, data, **_kw) -> Dict[str, Any]:
-        c = self._get(collection_name)
-        rows = [data] if isinstance(data, dict) else list(data)
-        ids = []
-        first_new = len(c.pks)
+    def _append_rows(self, c: _Collection, rows) -> List[int]:
+        """Validate ``rows`` and append them to the host lists and, when the collection has one, to the resident bank (fp32 rows: the
+        kernel decides whether they are fp16-exact).  Nothing is written to the file.  -> their primary keys."""
         for r in rows:      # validate the whole request before any row lands (a bad row rejects the request)
             if np.asarray(r[c.vector_field]).shape != (c.dim,):
                 raise MilvusException(1100, f"the dim ({np.asarray(r[c.vector_field]).size}) of field data"
                                             f"({c.vector_field}) is not equal to schema dim ({c.dim})")
-        for r in rows:
-            vec = np.asarray(r[c.vector_field], dtype=np.float32)
-            if vec.shape != (c.dim,):
-                raise MilvusException(1100, f"the dim ({vec.size}) of field data({c.vector_field}) is not "
-                                            f"equal to schema dim ({c.dim})")
+        vecs = [np.asarray(r[c.vector_field], dtype=np.float32) for r in rows]
+        if c._bank is not None and vecs:
+            from .._lib import AsttsError
+            try:
+                c._bank.append(np.stack(vecs))      # first: a refused batch (non-finite values) leaves bank and lists as they were
+            except AsttsError as e:
+                raise MilvusException(1100, f"insert refused: {e}") from None
+        ids = []
+        for r, vec in zip(rows, vecs):
             c.vectors.append(vec)
             pk = (max(c.pks) + 1 if c.pks else 1) if c.auto_id else int(r.get(c.pk_field, len(c.pks)))
             c.pks.append(pk)
             ids.append(pk)
             c.metas.append({k: v for k, v in r.items() if k not in (c.vector_field, c.pk_field)})
-        c._bank = None
+            c.live.append(True)
+        c.n_live += len(rows)
+        return ids
+
+    def _tombstone(self, c: _Collection, rows: Sequence[int]) -> int:
+        """Delete the live rows among ``rows`` on the host and in the resident bank.  -> how many were live."""
+        rows = [int(i) for i in rows if c.live[int(i)]]
+        for i in rows:
+            c.live[i] = False
+        c.n_live -= len(rows)
+        if rows and c._bank is not None:
+            c._bank.delete_rows(rows)
+        return len(rows)
+
+    def _rewrite(self, c: _Collection) -> None:
+        """delete / upsert / compact in the Milvus-Lite file: the collection is written again from its live rows, in order (the
+        existing writer; Milvus-Lite's own delete records are not reproduced).  Reopening the file shows the live rows, compacted."""
+        f = self._file()
+        if not f:
+            return
+        f.drop_collection(c.name)
+        f.create_collection(c.name, c.dim, c.metric, c.pk_field, c.vector_field)
+        f.insert(c.name, ((c.pks[i], c.vectors[i], c.metas[i]) for i in c.live_rows()), c.pk_field, c.vector_field)
+
+    def insert(self, collection_name: str, data, **_kw) -> Dict[str, Any]:
+        c = self._get(collection_name)
+        rows = [data] if isinstance(data, dict) else list(data)
+        first_new = len(c.pks)
+        ids = self._append_rows(c, rows)
         if self._file():
             self._file().insert(c.name, ((c.pks[i], c.vectors[i], c.metas[i]) for i in range(first_new, len(c.pks))),
                                 c.pk_field, c.vector_field)
         return {"insert_count": len(rows), "ids": ids}
+
+    def _select(self, c: _Collection, ids, filter: Optional[str]) -> List[int]:
+        """The live rows whose primary key is in ``ids`` (when given) and that satisfy ``filter`` (when given), in row order."""
+        keep = np.asarray(c.live, dtype=bool)
+        if ids is not None:
+            want = {int(i) for i in ([ids] if isinstance(ids, (int, np.integer)) else ids)}
+            keep &= np.fromiter((pk in want for pk in c.pks), dtype=bool, count=len(c.pks))
+        if filter:
+            from ..milvus_filter import FilterSyntaxError, row_mask
+            try:
+                keep &= row_mask(filter, c.pk_field, c.pks, c.metas).astype(bool)
+            except FilterSyntaxError as e:
+                raise MilvusException(1100, f"failed to create query plan: cannot parse expression: {filter}, error: {e}") from None
+        return [int(i) for i in np.flatnonzero(keep)]
+
+    def delete(self, collection_name: str, ids=None, filter: Optional[str] = None, **_kw) -> Dict[str, Any]:
+        """Exactly one of ``ids`` (one primary key or a list) / ``filter``.  -> ``{"delete_count": rows deleted}``: every live row
+        with one of the keys (the reference's keys are not unique), or that satisfies the filter."""
+        c = self._get(collection_name)
+        if (ids is None) == (not filter):
+            raise MilvusException(1, "delete needs exactly one of ids and filter")
+        count = self._tombstone(c, self._select(c, ids, filter))
+        if count:
+            self._rewrite(c)
+        return {"delete_count": count}
+
+    def upsert(self, collection_name: str, data, **_kw) -> Dict[str, Any]:
+        """For each row: every live row with its primary key is deleted, then the row is inserted.  -> ``{"upsert_count": n}``."""
+        c = self._get(collection_name)
+        rows = [data] if isinstance(data, dict) else list(data)
+        first_new = len(c.pks)
+        keys = {int(r[c.pk_field]) for r in rows if c.pk_field in r}
+        old = self._select(c, keys, None) if keys else []
+        ids = self._append_rows(c, rows)      # (first: a request that is refused deletes nothing)
+        self._tombstone(c, old)
+        last = {pk: first_new + j for j, pk in enumerate(ids)}      # of rows of this request that share a key, the last one stays
+        self._tombstone(c, [first_new + j for j, pk in enumerate(ids) if last[pk] != first_new + j])
+        self._rewrite(c)
+        return {"upsert_count": len(rows)}
+
+    def query(self, collection_name: str, filter: str = "", output_fields: Optional[Sequence[str]] = None, limit: Optional[int] = None,
+              ids=None, **_kw) -> List[Dict[str, Any]]:
+        """The live rows that satisfy ``filter`` / carry one of ``ids``, in row order, at most ``limit``: dicts with the primary key
+        and the fields of ``output_fields`` (``["*"]``: every scalar field; the vector only when it is named)."""
+        c = self._get(collection_name)
+        if not filter and ids is None and limit is None:
+            raise MilvusException(1100, "empty expression should be used with limit")
+        if limit is not None and int(limit) < 1:
+            raise MilvusException(1, f"limit {limit} is invalid")
+        rows = self._select(c, ids, filter)
+        fields = list(output_fields or [])
+        out = []
+        for i in rows[:None if limit is None else int(limit)]:
+            rec = {c.pk_field: c.pks[i]}
+            for f in fields:
+                if f == "*":
+                    rec.update(c.metas[i])
+                elif f == c.vector_field:
+                    rec[f] = c.vectors[i].tolist()
+                elif f in c.metas[i]:
+                    rec[f] = c.metas[i][f]
+            out.append(rec)
+        return out
+
+    def get(self, collection_name: str, ids, output_fields: Optional[Sequence[str]] = None, **_kw) -> List[Dict[str, Any]]:
+        return self.query(collection_name, ids=ids, output_fields=output_fields)
+
+    def get_collection_stats(self, collection_name: str, **_kw) -> Dict[str, Any]:
+        return {"row_count": self._get(collection_name).n_live}
+
+    def compact(self, collection_name: str, **_kw) -> int:
+        """Drop the deleted rows from the host lists and from the resident bank; the rows that are left keep their order and are
+        renumbered (a hit's ``'row'``).  -> how many rows were removed (pymilvus returns a job id here)."""
+        c = self._get(collection_name)
+        removed = len(c.live) - c.n_live
+        if removed == 0:
+            return 0
+        if c._bank is not None:
+            if c.n_live == 0:      # (a bank holds at least one row)
+                c._bank.close()
+                c._bank = None
+            else:
+                old_to_new = c._bank.compact()
+                assert int((old_to_new >= 0).sum()) == c.n_live
+        keep = c.live_rows()
+        c.vectors, c.pks, c.metas = [c.vectors[i] for i in keep], [c.pks[i] for i in keep], [c.metas[i] for i in keep]
+        c.live = [True] * len(keep)
+        self._rewrite(c)
+        return removed
 
     # ------------------------------------------------------------------ search (the hot path)
     def search(self, collection_name: str, data, filter: Optional[str] = "", limit: int = 10,
@@ -239,7 +372,7 @@ class MilvusClient:
     def search_rows(self, collection_name: str, data, filter: Optional[str] = "", limit: int = 10, search_params: Optional[dict] = None,
                     anns_field: Optional[str] = None, metric_type: Optional[str] = None, param: Optional[dict] = None, **_kw):
         """The arithmetic half of ``search``: -> (row index int64 [Q, k], cosine similarity fp32 [Q, k]) as numpy arrays, -1 = no hit
-        (k = min(limit, rows); k = 0 columns for an empty collection).  Row index == style id.  The data-parallel drivers shard
+        (k = min(limit, live rows); k = 0 columns for an empty collection).  Row index == style id.  The data-parallel drivers shard
         THIS call over the ranks and all-gather its result (astts.parallel.sharded_search); ``hits_from_rows`` turns rows into the
         pymilvus result shape wherever the records are written."""
         c = self._get(collection_name)
@@ -261,17 +394,17 @@ class MilvusClient:
         if q.ndim != 2 or q.shape[1] != c.dim:
             raise MilvusException(1100, f"vector dimension mismatch, expected vector size(byte) {c.dim * 4}, "
                                         f"actual {q.shape[-1] * 4}")
-        if len(c.pks) == 0:
+        if c.n_live == 0:
             return np.zeros((q.shape[0], 0), np.int64), np.zeros((q.shape[0], 0), np.float32)
         if limit < 1:
             raise MilvusException(1, f"limit {limit} is invalid")
-        k = min(int(limit), len(c.pks))
+        k = min(int(limit), c.n_live)
         from .._lib import KNN_MAX_K
         if k > KNN_MAX_K:
             # pymilvus accepts limit up to 16384; the reference asks for 1 or 3 (milvus/search_json.py:411,
             # milvus/search_embeddings.py:64).  Here: 32 certified hits per selection pass, at most 32 passes.
             raise MilvusException(1100, f"limit {limit} is not supported by this build: at most {KNN_MAX_K} hits per query "
-                                        f"(collection holds {len(c.pks)} rows)")
+                                        f"(collection holds {c.n_live} rows)")
         idx, score = c.bank().search(q, k, row_mask=mask) if mask is not None else c.bank().search(q, k)
         return np.asarray(idx, dtype=np.int64), np.asarray(score, dtype=np.float32)
 

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _lib_knn
 
 
 KNN_SCANS = ("DIRECT", "REGISTER", "GEMM", "GEMM_BLOCKS", "GEMM_N_FIRST")      # ASTTS_KNN_SCAN_*
@@ -53,6 +53,12 @@ class StyleBank:
     """``N x D`` style-embedding bank held on one GPU.
 
     ``vectors``: numpy / torch array ``[N, D]`` (fp16 or fp32).  Row index == style id.
+
+    The bank can change while it stays on the GPU (include/knn/astts_knn_mutable.h): ``append`` packs the new rows behind the old ones
+    (cost O(new rows); a grown bank returns bit for bit what a bank created at once from the same rows returns), ``delete_rows``
+    tombstones rows (no search returns them; row indices stay), ``compact`` squeezes the tombstones out and renumbers.  ``n`` rows,
+    ``live`` of them not deleted, ``capacity`` rows allocated.  None of these may run while a search of this bank is in flight on
+    another stream or thread.
     """
 
     def __init__(self, vectors, device: Optional[torch.device] = None, metric: str = "COSINE"):
@@ -81,14 +87,73 @@ class StyleBank:
                 metric_id, _lib.stream_ptr(), ctypes.byref(h)))
         self._h = h
         self.metric = metric.upper()
-        self.n, self.d = int(src.shape[0]), int(src.shape[1])
-        exact = ctypes.c_int32()
-        _lib.check(lib.astts_knn_info(self._h, None, None, ctypes.byref(exact)))
-        self.scan_plane_exact = bool(exact.value)
+        self.d = int(src.shape[1])
         self._ws: Optional[torch.Tensor] = None
         self._ws_key: Tuple[int, int] = (0, 0)
         self._plans: dict = {}                       # (nq, k) -> (workspace tensor, aligned pointer, bytes)
         self._search = lib.astts_knn_search
+        self._refresh()
+
+    def _refresh(self) -> None:
+        """``n``, ``live``, ``capacity`` and ``scan_plane_exact`` from the handle; the workspace plans are per (n, tombstone state)."""
+        n, live, cap, exact = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        _lib.check(_lib_knn.load().astts_knn_stats(self._h, ctypes.byref(n), ctypes.byref(live), ctypes.byref(cap)))
+        _lib.check(_lib.load().astts_knn_info(self._h, None, None, ctypes.byref(exact)))
+        self.n, self.live, self.capacity = int(n.value), int(live.value), int(cap.value)
+        self.scan_plane_exact = bool(exact.value)
+        self._plans = {}
+
+    # ---- mutation (each call synchronises the current stream, as the constructor does)
+    def reserve(self, capacity: int) -> None:
+        """Room for ``capacity`` rows (rounded up to a multiple of 128; never shrinks), so that appends up to it copy nothing."""
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(_lib_knn.load().astts_knn_reserve(self._h, int(capacity), _lib.stream_ptr()))
+            finally:
+                self._refresh()
+
+    def append(self, vectors) -> int:
+        """``vectors``: numpy / torch ``[M, D]`` (or one ``[D]`` row), fp16 or fp32 -> the row index of the first new row.  fp32 rows
+        that are not fp16-exact promote an fp16-exact bank (``scan_plane_exact`` turns False).  Non-finite values raise
+        (ASTTS_ERR_RANGE) and leave the bank as it was."""
+        t = torch.from_numpy(np.ascontiguousarray(vectors)) if isinstance(vectors, np.ndarray) else torch.as_tensor(vectors)
+        if t.dim() == 1:
+            t = t[None, :]
+        if t.dim() != 2 or t.shape[1] != self.d:
+            raise ValueError(f"rows must be [M, {self.d}], got {tuple(t.shape)}")
+        if t.dtype not in (torch.float16, torch.float32):
+            t = t.to(torch.float32)
+        first = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            src = t.to(self.device).contiguous()
+            try:
+                _lib.check(_lib_knn.load().astts_knn_append(self._h, src.data_ptr(), src.shape[0],
+                                                            _lib.DTYPE_F16 if src.dtype == torch.float16 else _lib.DTYPE_F32,
+                                                            _lib.stream_ptr(), ctypes.byref(first)))
+            finally:
+                self._refresh()
+        return int(first.value)
+
+    def delete_rows(self, rows) -> None:
+        """Tombstone ``rows`` (indices into the bank): no search returns them.  A row outside ``[0, n)`` raises and deletes nothing;
+        deleting a row twice is harmless."""
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1))
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(_lib_knn.load().astts_knn_set_deleted(self._h, r.ctypes.data, int(r.size), _lib.stream_ptr()))
+            finally:
+                self._refresh()
+
+    def compact(self) -> np.ndarray:
+        """Remove the tombstoned rows; the survivors keep their order.  -> int64 ``[old n]``: the new index of every old row, -1 for
+        a removed one.  A bank whose rows are all deleted cannot be compacted (ASTTS_ERR_UNSUPPORTED): close it."""
+        old_to_new = np.empty(self.n, dtype=np.int64)
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(_lib_knn.load().astts_knn_compact(self._h, _lib.stream_ptr(), None, old_to_new.ctypes.data))
+            finally:
+                self._refresh()
+        return old_to_new
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -180,8 +245,9 @@ class StyleBank:
         return idx.cpu().numpy(), sc.cpu().numpy()
 
     def route(self, nq: int, k: int, masked: bool = False, aligned: bool = True):
-        """``route`` (above) for a search of this bank: ``[(rows, scan, finish), ...]``, one per query group."""
-        return route(self.n, self.d, nq, k, masked, aligned)
+        """``route`` (above) for a search of this bank: ``[(rows, scan, finish), ...]``, one per query group.  A bank with tombstones
+        searches as a masked one."""
+        return route(self.n, self.d, nq, k, masked or self.live < self.n, aligned)
 
     def last_fallbacks(self) -> int:
         """How many queries of the last search needed the exact fp64 scan (synchronises)."""

@@ -10,8 +10,10 @@
 // Optional row mask (a Milvus `filter` evaluated by the host, or the rows already returned by earlier passes of a
 // k > 32 search): masked rows are never candidates, in the approximate and in the exact path alike.
 //
-// This file: the handle, the plan of a search (make_plan: the ONE place that decides its query groups and every group's (scan, finish)
-// route), one launcher per step and the C entry points.  The kernels: knn_kernels.h.
+// This file: creation of the handle (the struct and its layout invariants: knn_handle.h), the plan of a search (make_plan: the ONE place
+// that decides its query groups and every group's (scan, finish) route), one launcher per step and the C entry
+// points.  The kernels: knn_kernels.h.  Appending rows, tombstones and compaction: knn_mutable.hip.  A handle with tombstones
+// (h->live) searches as a masked one: its live mask is the row mask, ANDed with the caller's when there is one.
 //
 // Pipeline (five launches on one stream, no host sync, no allocation):
 //   1 knn_prep_queries     fp32 queries -> power-of-two scaled fp16 image + padded fp32 copy + fp64 norms
@@ -29,6 +31,7 @@
 // padded to a multiple of 32 with zeros.  The EXACT plane (fp64 re-score / exact path) stays row-major [N][Dp]:
 // fp16 when the bank is fp16-exact, else fp32.  fp64 row norms [N]; fp32 inverse norms [N].
 #include "common.h"
+#include "knn_handle.h"
 #include "knn_kernels.h"
 
 #include <cstdlib>
@@ -40,24 +43,7 @@
 // ==========================================================================================
 using namespace astts;
 
-struct astts_knn {
-    int64_t n = 0;
-    int d = 0, dp = 0, nld = 0;
-    int metric = 0;
-    bool exact16 = true;          // scan plane is a lossless image of the bank
-    _Float16* scan = nullptr;     // tiled scan plane [ceil(n/128)*4 row tiles][dp/64][4][64][8]
-    _Float16* plane16 = nullptr;  // [n][dp] row-major (exact plane when exact16), zero rows up to a multiple of 128 behind it
-    float* plane32 = nullptr;     // [n][dp], only when !exact16
-    double* norm64 = nullptr;     // [n]
-    float* inv_norm = nullptr;    // [n]  COSINE: 1 / |b| (x the row's power-of-two scale); IP / L2: that scale alone
-    float* bias = nullptr;        // [n]  L2 only: -|b|^2 / 2
-    double bmax = 0.0;            // largest row norm (IP / L2 certification works on the absolute scale)
-    double err_bound = 0.0;
-    // bench-only profiling (astts_knn_profile_*)
-    bool profile = false;
-    std::vector<hipEvent_t> ev;  // pairs (start, stop)
-    size_t ev_used = 0;
-};
+static_assert(kKnnMaxRows == (int64_t)1024 * kSelSeg, "the row limit of the handle is 1024 selection segments");
 
 namespace {
 
@@ -106,9 +92,11 @@ struct KnnPlan {
 // The ONE place that decides how a search runs: scan geometry, query groups, every group's (scan, finish) route, workspace layout.
 // astts_knn_search launches what it says and astts_knn_route reports it.  masked: a caller's row mask; aligned: the caller's queries
 // sit at a 16-byte aligned address; ring_ok: gemm_scan_blockmax_ok for this bank (the ring kernels will carry the block-maximum
-// epilogue) -- these three and sw.no_direct / no_stream / no_blocks / n_first choose among routes, never the layout.
-KnnPlan make_plan(int64_t n, int d, int nq, int k, bool masked, bool aligned, const KnnSwitches& sw, bool ring_ok) {
+// epilogue) -- these three and sw.no_direct / no_stream / no_blocks / n_first choose among routes, never the layout.  tomb: the bank
+// has tombstones -- its search is a masked one, and the workspace holds the live mask ANDed with the caller's (up to one per query).
+KnnPlan make_plan(int64_t n, int d, int nq, int k, bool masked, bool aligned, const KnnSwitches& sw, bool ring_ok, bool tomb = false) {
     KnnPlan p{};
+    masked = masked || tomb;
     const int dp = (int)align_up((size_t)d, 64), nld = (int)align_up((size_t)n, 128);
     const bool single = k <= kPassK && nq <= kMaxQPerPass;      // one pass and one query group: the whole search can finish in one launch
     p.passes = 1;
@@ -194,7 +182,7 @@ KnnPlan make_plan(int64_t n, int d, int nq, int k, bool masked, bool aligned, co
     p.off_cs = take(sizeof(float) * (size_t)nq * 64);
     p.off_sidx = take(sizeof(int) * (size_t)kMaxQPerPass * p.nseg * 64);
     p.off_ss = take(sizeof(float) * (size_t)kMaxQPerPass * p.nseg * 64);
-    p.off_mask = take(multi ? (size_t)nq * (size_t)n : 16);
+    p.off_mask = take(multi || tomb ? (size_t)nq * (size_t)n : 16);
     p.off_bmax = take(p.gemm && p.nblk <= kSelSeg ? sizeof(float) * (size_t)kMaxQPerPass * p.bm_ld : 16);
     p.total = o;
     return p;
@@ -202,9 +190,10 @@ KnnPlan make_plan(int64_t n, int d, int nq, int k, bool masked, bool aligned, co
 
 // the plan under the switches and the ring kernels' state in force (astts_op_gemm_set_ring_mode / ASTTS_GEMM_RING).  ws: the search's
 // workspace, where the GEMM's fp16 query rows sit at multiples of 128 bytes (null: a host query, no workspace yet)
-KnnPlan plan_search(int64_t n, int d, int nq, int k, bool masked, bool aligned, const void* ws) {
+KnnPlan plan_search(int64_t n, int d, int nq, int k, bool masked, bool aligned, const void* ws, bool tomb = false) {
     const int qgroup = nq < kMaxQPerPass ? nq : kMaxQPerPass;
-    return make_plan(n, d, nq, k, masked, aligned, knn_switches(), gemm_scan_blockmax_ok(qgroup, n, (int)align_up((size_t)d, 64), ws));
+    return make_plan(n, d, nq, k, masked, aligned, knn_switches(), gemm_scan_blockmax_ok(qgroup, n, (int)align_up((size_t)d, 64), ws),
+                     tomb);
 }
 
 template <int QT, int RT, bool DIRECT = false>
@@ -232,6 +221,39 @@ int launch_scan(const astts_knn* h, const KnnPlan& p, const _Float16* qh, int nq
 
 }  // namespace
 
+namespace astts {
+
+int knn_build_rows(astts_knn* h, const void* rows, int64_t row0, int64_t m, int dtype, int* flags, hipStream_t st) {
+    const int rows_per_block = 4;
+    dim3 grid((unsigned)cdiv(m, rows_per_block));
+    if (dtype == ASTTS_DTYPE_F32)
+        hipLaunchKernelGGL((knn_build_bank<float>), grid, dim3(256), 0, st, (const float*)rows, row0, row0 + m, h->d, h->dp, h->scan,
+                           h->plane16, h->plane32, h->norm64, h->inv_norm, flags, h->metric, h->bias);
+    else
+        hipLaunchKernelGGL((knn_build_bank<_Float16>), grid, dim3(256), 0, st, (const _Float16*)rows, row0, row0 + m, h->d, h->dp, h->scan,
+                           h->plane16, h->plane32, h->norm64, h->inv_norm, flags, h->metric, h->bias);
+    ASTTS_CHECK_LAUNCH();
+    return ASTTS_OK;
+}
+
+int knn_rescale(astts_knn* h, int64_t row0, int64_t m, hipStream_t st) {
+    hipLaunchKernelGGL(knn_rescale_rows, dim3((unsigned)cdiv(m, 4)), dim3(256), 0, st, h->plane32, row0, row0 + m, h->dp, h->scan, h->plane16,
+                       h->norm64, h->inv_norm, h->metric);
+    ASTTS_CHECK_LAUNCH();
+    return ASTTS_OK;
+}
+
+// Error bound of the fp16 scan on the cosine scale (DESIGN.md "certification"):
+//   query rounded to fp16 (11-bit significand, power-of-two pre-scale): 2^-11 (Cauchy-Schwarz)
+//   fp32 accumulation of dp exact products inside the MFMA chain + cross-wave/ksplit adds: 2*dp*2^-24
+//   bank rounded to fp16 when it is not fp16-exact: 2^-11
+//   inv_norm rounding, final scaling: 2^-20
+void knn_set_err_bound(astts_knn* h) {
+    h->err_bound = ldexp(1.0, -11) + 2.0 * (double)h->dp * ldexp(1.0, -24) + ldexp(1.0, -20) + (h->exact16 ? 0.0 : ldexp(1.0, -11));
+}
+
+}  // namespace astts
+
 extern "C" {
 
 int astts_knn_create(const void* bank, int64_t n, int32_t d, int32_t dtype, int32_t metric,
@@ -254,12 +276,11 @@ int astts_knn_create(const void* bank, int64_t n, int32_t d, int32_t dtype, int3
     h->d = d;
     h->dp = (int)align_up((size_t)d, 64);
     h->nld = (int)align_up((size_t)n, 128);
+    h->capacity = h->nld;         // exactly the tiles of the bank: the first append over a tile edge grows it (astts_knn_append)
     h->metric = metric;
     int* flags = nullptr;
-    float* p32 = nullptr;
     auto fail = [&](int code) {
         if (flags) (void)hipFree(flags);
-        if (p32) (void)hipFree(p32);
         astts_knn_destroy(h);
         return code;
     };
@@ -271,29 +292,20 @@ int astts_knn_create(const void* bank, int64_t n, int32_t d, int32_t dtype, int3
             return fail(ASTTS_ERR_HIP);                                                      \
         }                                                                                    \
     } while (0)
-    const size_t scan_rows = align_up((size_t)n, 128);  // every row tile a scan block may touch exists
-    KNN_TRY(hipMalloc(&h->scan, sizeof(_Float16) * scan_rows * h->dp));
-    KNN_TRY(hipMemsetAsync(h->scan, 0, sizeof(_Float16) * scan_rows * h->dp, st));
+    const size_t cap = (size_t)h->capacity;  // every row tile a scan block may touch exists
+    KNN_TRY(hipMalloc(&h->scan, sizeof(_Float16) * cap * h->dp));
+    KNN_TRY(hipMemsetAsync(h->scan, 0, sizeof(_Float16) * cap * h->dp, st));
     // (the row-major plane is the GEMM scan's "weight" matrix: the ring kernels clamp their row index to n - 1, the tile kernels that
     // serve the GEMM while the ring kernels are switched off read whole tiles of up to 128 rows -- rows of zeros behind the bank)
-    KNN_TRY(hipMalloc(&h->plane16, sizeof(_Float16) * scan_rows * h->dp));
-    if (scan_rows > (size_t)n) KNN_TRY(hipMemsetAsync(h->plane16 + (size_t)n * h->dp, 0, sizeof(_Float16) * (scan_rows - (size_t)n) * h->dp, st));
-    KNN_TRY(hipMalloc(&h->norm64, sizeof(double) * (size_t)n));
-    KNN_TRY(hipMalloc(&h->inv_norm, sizeof(float) * (size_t)n));
-    if (metric == ASTTS_METRIC_L2) KNN_TRY(hipMalloc(&h->bias, sizeof(float) * (size_t)n));
+    KNN_TRY(hipMalloc(&h->plane16, sizeof(_Float16) * cap * h->dp));
+    if (cap > (size_t)n) KNN_TRY(hipMemsetAsync(h->plane16 + (size_t)n * h->dp, 0, sizeof(_Float16) * (cap - (size_t)n) * h->dp, st));
+    KNN_TRY(hipMalloc(&h->norm64, sizeof(double) * cap));
+    KNN_TRY(hipMalloc(&h->inv_norm, sizeof(float) * cap));
+    if (metric == ASTTS_METRIC_L2) KNN_TRY(hipMalloc(&h->bias, sizeof(float) * cap));
     KNN_TRY(hipMalloc(&flags, 4 * sizeof(int)));
     KNN_TRY(hipMemsetAsync(flags, 0, 4 * sizeof(int), st));
-    const int rows_per_block = 4;
-    dim3 grid((unsigned)cdiv(n, rows_per_block));
-    if (dtype == ASTTS_DTYPE_F32) {
-        KNN_TRY(hipMalloc(&p32, sizeof(float) * (size_t)n * h->dp));
-        hipLaunchKernelGGL((knn_build_bank<float>), grid, dim3(256), 0, st, (const float*)bank, n, d,
-                           h->dp, h->scan, h->plane16, p32, h->norm64, h->inv_norm, flags, metric, h->bias);
-    } else {
-        hipLaunchKernelGGL((knn_build_bank<_Float16>), grid, dim3(256), 0, st, (const _Float16*)bank,
-                           n, d, h->dp, h->scan, h->plane16, (float*)nullptr, h->norm64, h->inv_norm, flags, metric, h->bias);
-    }
-    KNN_TRY(hipGetLastError());
+    if (dtype == ASTTS_DTYPE_F32) KNN_TRY(hipMalloc(&h->plane32, sizeof(float) * cap * h->dp));      // kept when the bank is not fp16-exact
+    if (knn_build_rows(h, bank, 0, n, dtype, flags, st) != ASTTS_OK) return fail(ASTTS_ERR_HIP);
     int hf[4] = {0, 0, 0, 0};
     KNN_TRY(hipMemcpyAsync(hf, flags, sizeof(hf), hipMemcpyDeviceToHost, st));
     KNN_TRY(hipStreamSynchronize(st));
@@ -304,27 +316,17 @@ int astts_knn_create(const void* bank, int64_t n, int32_t d, int32_t dtype, int3
     }
     h->exact16 = (hf[0] == 0);
     if (!h->exact16) {
-        h->plane32 = p32;  // keep the fp32 image for exact re-scoring
-        p32 = nullptr;
-        // approximate planes re-written with a per-row power-of-two scale (see knn_rescale_rows)
-        hipLaunchKernelGGL(knn_rescale_rows, grid, dim3(256), 0, st, h->plane32, n, h->dp, h->scan, h->plane16, h->norm64, h->inv_norm, metric);
-        KNN_TRY(hipGetLastError());
+        // the fp32 image stays for exact re-scoring; approximate planes re-written with a per-row power-of-two scale (see knn_rescale_rows)
+        if (knn_rescale(h, 0, n, st) != ASTTS_OK) return fail(ASTTS_ERR_HIP);
         KNN_TRY(hipStreamSynchronize(st));
+    } else if (h->plane32) {
+        (void)hipFree(h->plane32);
+        h->plane32 = nullptr;
     }
     (void)hipFree(flags);
     flags = nullptr;
-    if (p32) {
-        (void)hipFree(p32);
-        p32 = nullptr;
-    }
 #undef KNN_TRY
-    // Error bound of the fp16 scan on the cosine scale (DESIGN.md "certification"):
-    //   query rounded to fp16 (11-bit significand, power-of-two pre-scale): 2^-11 (Cauchy-Schwarz)
-    //   fp32 accumulation of dp exact products inside the MFMA chain + cross-wave/ksplit adds: 2*dp*2^-24
-    //   bank rounded to fp16 when it is not fp16-exact: 2^-11
-    //   inv_norm rounding, final scaling: 2^-20
-    h->err_bound = ldexp(1.0, -11) + 2.0 * (double)h->dp * ldexp(1.0, -24) + ldexp(1.0, -20) +
-                   (h->exact16 ? 0.0 : ldexp(1.0, -11));
+    knn_set_err_bound(h);
     *out = h;
     return ASTTS_OK;
 }
@@ -337,6 +339,7 @@ int astts_knn_destroy(astts_knn_t* h) {
     if (h->norm64) (void)hipFree(h->norm64);
     if (h->inv_norm) (void)hipFree(h->inv_norm);
     if (h->bias) (void)hipFree(h->bias);
+    if (h->live) (void)hipFree(h->live);
     for (auto& e : h->ev) (void)hipEventDestroy(e);
     delete h;
     return ASTTS_OK;
@@ -352,7 +355,8 @@ int astts_knn_info(const astts_knn_t* h, int64_t* n, int32_t* d, int32_t* scan_p
 
 size_t astts_knn_workspace_bytes(const astts_knn_t* h, int32_t nq, int32_t k) {
     if (!h || nq < 1 || k < 1 || k > ASTTS_KNN_MAX_K) return 0;
-    return make_plan(h->n, h->d, nq, k, false, true, knn_switches(), false).total;      // (the layout does not depend on the route)
+    // (the layout does not depend on the route; it follows the current n, and a bank with tombstones adds the combined mask)
+    return make_plan(h->n, h->d, nq, k, false, true, knn_switches(), false, h->live != nullptr).total;
 }
 
 }  // extern "C"
@@ -503,15 +507,21 @@ int knn_search_chunk(astts_knn* h, const KnnPlan& p, const float* queries, int n
     float *qf = (float*)(ws + p.off_qf), *qscale = (float*)(ws + p.off_qscale);
     double* qn = (double*)(ws + p.off_qn);
     uint8_t* own_mask = (uint8_t*)(ws + p.off_mask);
+    // The mask the kernels see.  k > 32: per-query masks in the workspace.  A bank with tombstones: its live mask, ANDed into the
+    // workspace with the caller's when there is one (one row for a shared mask, else one per query).  Otherwise the caller's, as is.
+    const bool own = multi || (h->live && row_mask);
+    const int own_rows = multi || mask_stride ? nq : 1;
+    const uint8_t* const mask = own ? own_mask : h->live ? h->live : row_mask;
+    const int64_t mstride = own ? (own_rows > 1 || multi ? h->n : 0) : h->live ? 0 : mask_stride;
     const KnnChunk c{h, p, st, queries, nq, (_Float16*)(ws + p.off_qh), p.gemm ? (_Float16*)(ws + p.off_qrow) : nullptr,
                      (float*)(ws + p.off_spart), (int*)(ws + p.off_cidx), (float*)(ws + p.off_cs), (int*)(ws + p.off_sidx),
-                     (float*)(ws + p.off_ss), (float*)(ws + p.off_bmax), multi ? own_mask : row_mask, multi ? h->n : mask_stride,
+                     (float*)(ws + p.off_ss), (float*)(ws + p.off_bmax), mask, mstride,
                      // (direct: no preparation launch -- the finish reads the caller's queries and forms their norms itself)
                      KnnRescoreArgs{direct ? queries : qf, qn, qscale, h->norm64, h->n, h->dp, p.c, k, h->err_bound,
                                     (flags & ASTTS_KNN_FORCE_EXACT) ? 1 : 0, out_idx, out_score, out_score64, nflag, h->metric, h->bmax}};
-    if (multi) {
-        hipLaunchKernelGGL(knn_mask_init, dim3((unsigned)(cdiv(h->n, 256 * 16) < 1024 ? cdiv(h->n, 256 * 16) : 1024), nq), dim3(256), 0, st,
-                           own_mask, row_mask, mask_stride, h->n);
+    if (own) {
+        hipLaunchKernelGGL(knn_mask_init, dim3((unsigned)(cdiv(h->n, 256 * 16) < 1024 ? cdiv(h->n, 256 * 16) : 1024), own_rows), dim3(256), 0,
+                           st, own_mask, row_mask, mask_stride, h->n, (const uint8_t*)h->live);
         ASTTS_CHECK_LAUNCH();
     }
     if (!direct) {
@@ -563,7 +573,7 @@ int astts_knn_search(astts_knn_t* h, const float* queries, int32_t nq, int32_t k
                   "astts_knn_search: mask_stride %lld (0 = one mask for every query, else >= n = %lld)", (long long)mask_stride, (long long)h->n);
     ASTTS_REQUIRE(workspace != nullptr && ((uintptr_t)workspace & 255) == 0, ASTTS_ERR_WORKSPACE,
                   "astts_knn_search: workspace must be 256-byte aligned");
-    const KnnPlan p = plan_search(h->n, h->d, nq, k, row_mask != nullptr, ((uintptr_t)queries & 15) == 0, workspace);
+    const KnnPlan p = plan_search(h->n, h->d, nq, k, row_mask != nullptr, ((uintptr_t)queries & 15) == 0, workspace, h->live != nullptr);
     ASTTS_REQUIRE(workspace_bytes >= p.total, ASTTS_ERR_WORKSPACE,
                   "astts_knn_search: workspace %zu < required %zu", workspace_bytes, p.total);
     const int chunk = p.passes == 1 ? nq : kMaxQPerPass;      // k > 32: chunks of <= 256 queries share the workspace, in stream order

@@ -164,16 +164,17 @@ __device__ __forceinline__ double user_score(int metric, double s) { return metr
 // bank construction: one wave per row -- copy/convert into the padded planes, fp64 norm,
 // exactness + range flags
 // ------------------------------------------------------------------------------------------
+// Rows [row0, n) of the planes from src[0 .. n - row0): row0 = 0 builds a bank, row0 > 0 appends behind its rows without touching them.
 template <typename SrcT>
-__global__ void knn_build_bank(const SrcT* __restrict__ src, int64_t n, int d, int dp,
+__global__ void knn_build_bank(const SrcT* __restrict__ src, int64_t row0, int64_t n, int d, int dp,
                                _Float16* __restrict__ scan_tiled, _Float16* __restrict__ plane16,
                                float* __restrict__ plane32, double* __restrict__ norm64,
                                float* __restrict__ inv_norm, int* __restrict__ flags /* [0]=inexact, [1]=overflow, [2..3]=max norm (fp64 bits) */,
                                int metric, float* __restrict__ bias /* L2: -|b|^2 / 2 */) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6);
+    const int64_t row = row0 + (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6);
     if (row >= n) return;
-    const SrcT* s = src + row * (int64_t)d;
+    const SrcT* s = src + (row - row0) * (int64_t)d;
     double acc = 0.0;
     bool inexact = false, overflow = false;
     for (int k = lane; k < dp; k += kWave) {
@@ -211,10 +212,10 @@ __global__ void knn_build_bank(const SrcT* __restrict__ src, int64_t n, int d, i
 // query.  The scale is folded into inv_norm (exactly: a power of two); the exact plane (plane32) and the fp64 norms keep the
 // original values.  Elements more than 2^37 below their row's maximum still flush: |error| <= sqrt(dp) * 2^-38 on the cosine
 // scale, inside the 2^-20 term of the bound.
-__global__ void knn_rescale_rows(const float* __restrict__ plane32, int64_t n, int dp, _Float16* __restrict__ scan_tiled,
+__global__ void knn_rescale_rows(const float* __restrict__ plane32, int64_t row0, int64_t n, int dp, _Float16* __restrict__ scan_tiled,
                                  _Float16* __restrict__ plane16, const double* __restrict__ norm64, float* __restrict__ inv_norm, int metric) {
     const int lane = threadIdx.x & 63;
-    const int64_t row = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6);
+    const int64_t row = row0 + (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6);
     if (row >= n) return;
     const float* s = plane32 + row * (int64_t)dp;
     float mx = 0.0f;
@@ -1170,11 +1171,16 @@ __global__ void knn_mask_out(const int64_t* __restrict__ out_idx, int out_ld, in
         if (id >= 0) mask[(int64_t)q * n + id] = 0;
     }
 }
-// per-query masks of a k > 32 search: the caller's row mask (one for all queries, or one per query) or all ones
-__global__ void knn_mask_init(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t src_stride, int64_t n) {
+// The masks a search works on, one row of n bytes per blockIdx.y: the caller's row mask (one for all queries, or one per query; null:
+// all ones) AND the handle's live mask (null: a bank without tombstones).  The per-query masks of a k > 32 search, and the combined
+// mask of a single-pass search of a bank with tombstones under a caller's mask.
+__global__ void knn_mask_init(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, int64_t src_stride, int64_t n,
+                              const uint8_t* __restrict__ live) {
     const int q = blockIdx.y;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        dst[(int64_t)q * n + i] = src ? (src[(int64_t)q * src_stride + i] ? 1 : 0) : 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool on = (src ? src[(int64_t)q * src_stride + i] != 0 : true) && (live ? live[i] != 0 : true);
+        dst[(int64_t)q * n + i] = on ? 1 : 0;
+    }
 }
 
 // Selection + re-score in one launch when a query's score row is one segment (N <= 8192) and all queries fit one pass: the
