@@ -3,6 +3,7 @@ convention (the wrapper swallows search errors: print + traceback, return [] -- 
 style bank through the MilvusClient shim.
 
     python -m astts.cli.search_embeddings --query_embedding q.json --top_k 3 --db_path milvus_demo.db
+Beyond the reference: ``--group_by_field FIELD [--group_size N]`` returns the top_k closest groups of FIELD, N hits of each.
 """
 import argparse
 import json
@@ -11,11 +12,12 @@ import traceback
 from astts.compat.pymilvus import MilvusClient
 
 
-def search_milvus(client, collection_name, embedding, top_k=3):
+def search_milvus(client, collection_name, embedding, top_k=3, group_by_field=None, group_size=1):
     try:
         param = {"nprobe": 10}
+        grouping = {"group_by_field": group_by_field, "group_size": group_size} if group_by_field else {}
         return client.search(collection_name=collection_name, data=[embedding], anns_field="vector", param=param,
-                             limit=top_k, output_fields=["file_id", "text"])
+                             limit=top_k, output_fields=["file_id", "text"], **grouping)
     except Exception as e:  # noqa: BLE001 -- the reference degrades to [] on any failure
         print(f"Error during Milvus search: {e}")
         traceback.print_exc()
@@ -33,11 +35,14 @@ def main(args):
         print(f"Error loading query embedding: {e}")
         traceback.print_exc()
         return []
-    search_results = search_milvus(client, "embeddings_biographies_collection", query_embedding, top_k=args.top_k)
+    search_results = search_milvus(client, "embeddings_biographies_collection", query_embedding, top_k=args.top_k,
+                                   group_by_field=args.group_by_field, group_size=args.group_size)
     if search_results:
         for i, result in enumerate(search_results):
             print(f"\nTop {args.top_k} results for Query {i + 1}:")
             for res in result:
+                if args.group_by_field:      # (top_k groups of up to group_size hits, in the order of their best hits)
+                    print(f"Group {args.group_by_field}={res['entity'].get(args.group_by_field)!r}: ", end="")
                 print(f"File ID: {res['entity']['file_id']}, Distance: {res['distance']}, Text: {res['entity']['text']}")
             print("-" * 50)
     else:
@@ -51,6 +56,10 @@ def build_parser():
                         help="Path to the JSON file containing the query embedding vector")
     parser.add_argument("--top_k", type=int, default=3, help="Number of top similar results to retrieve")
     parser.add_argument("--db_path", type=str, default="milvus_demo.db", help="Path to the Milvus Lite database file")
+    # not in the reference: grouped search of the style bank (off by default: output as the reference prints it)
+    parser.add_argument("--group_by_field", type=str, default=None,
+                        help="Return the top_k closest GROUPS of this scalar field (or the primary key) instead of the top_k hits")
+    parser.add_argument("--group_size", type=int, default=1, help="Hits per group (with --group_by_field)")
     return parser
 
 

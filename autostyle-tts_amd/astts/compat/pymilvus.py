@@ -13,6 +13,8 @@ Mirrors exactly the calls the reference makes (paths under /root/reference):
 and the calls that maintain a collection after ``insert`` (not made by the reference; pymilvus' names and result keys):
   .delete(collection_name, ids= | filter=) / .upsert(collection_name, data) / .query(...) / .get(collection_name, ids) /
   .get_collection_stats(collection_name) / .compact(collection_name)
+  .search(..., group_by_field=, group_size=, strict_group_size=, offset=, search_params={"params": {"radius":, "range_filter":}})
+                                                            the ``limit`` closest groups / the hits inside a score band: search_rows
   FieldSchema / CollectionSchema / DataType, .create_collection(schema=CollectionSchema(...)), .create_index(...)
                                                             milvus/insert_embeddings.py:52-79 (auto_id pk, VARCHAR fields)
 Result shape: ``list[Q]`` of ``list[k]`` of ``{'id': pk, 'distance': cosine_similarity,
@@ -97,7 +99,32 @@ class _Collection:
         self.live: List[bool] = []      # vectors / pks / metas / live are row-aligned with the bank; a deleted row stays until compact
         self.n_live = 0
         self._bank = None  # astts.knn.StyleBank, built lazily by the first search, then kept up to date in place
+        self._group_codes: Dict[str, Any] = {}      # group_by_field -> (int32 codes [rows], groups); dropped whenever the rows change
 
+    def group_codes(self, field: str):
+        """Dense group codes of the rows under ``field`` (a scalar field or the primary key), cached per field: -> (int32 ``[rows]``,
+        number of groups).  Equal values of one type share a code, in the order of their first row; a row without the field forms
+        a group of its own."""
+        if field == self.vector_field:
+            raise MilvusException(1100, f"unsupported field type for group by: field {field!r} is the vector field")
+        hit = self._group_codes.get(field)
+        if hit is not None:
+            return hit
+        if field != self.pk_field and not any(field in m for m in self.metas):
+            raise MilvusException(1100, f"groupBy field not found in schema: field not found[field={field}]")
+        codes = np.empty(len(self.pks), np.int32)
+        seen: Dict[Any, int] = {}
+        for i, meta in enumerate(self.metas):
+            if field == self.pk_field:
+                key = ("pk", self.pks[i])
+            elif field in meta:
+                v = meta[field]
+                key = (type(v).__name__, v if isinstance(v, (bool, int, float, str, bytes, type(None))) else repr(v))
+            else:
+                key = ("row", i)
+            codes[i] = seen.setdefault(key, len(seen))
+        self._group_codes[field] = (codes, max(len(seen), 1))
+        return self._group_codes[field]
     def live_rows(self) -> List[int]:
         return [i for i, on in enumerate(self.live) if on]
 
@@ -239,6 +266,7 @@ class MilvusClient:
             c.metas.append({k: v for k, v in r.items() if k not in (c.vector_field, c.pk_field)})
             c.live.append(True)
         c.n_live += len(rows)
+        c._group_codes = {}
         return ids
 
     def _tombstone(self, c: _Collection, rows: Sequence[int]) -> int:
@@ -247,6 +275,7 @@ class MilvusClient:
         for i in rows:
             c.live[i] = False
         c.n_live -= len(rows)
+        c._group_codes = {}
         if rows and c._bank is not None:
             c._bank.delete_rows(rows)
         return len(rows)
@@ -357,6 +386,7 @@ class MilvusClient:
         keep = c.live_rows()
         c.vectors, c.pks, c.metas = [c.vectors[i] for i in keep], [c.pks[i] for i in keep], [c.metas[i] for i in keep]
         c.live = [True] * len(keep)
+        c._group_codes = {}
         self._rewrite(c)
         return removed
 
@@ -364,18 +394,56 @@ class MilvusClient:
     def search(self, collection_name: str, data, filter: Optional[str] = "", limit: int = 10,
                output_fields: Optional[Sequence[str]] = None, search_params: Optional[dict] = None,
                anns_field: Optional[str] = None, metric_type: Optional[str] = None,
-               param: Optional[dict] = None, **_kw) -> List[List[Dict[str, Any]]]:
+               param: Optional[dict] = None, group_by_field: Optional[str] = None, group_size: int = 1,
+               strict_group_size: Optional[bool] = None, offset: int = 0, **_kw) -> List[List[Dict[str, Any]]]:
+        """``group_by_field`` (a scalar field or the primary key), ``group_size``, ``offset`` and ``radius`` / ``range_filter`` (in
+        ``search_params["params"]``, ``param["params"]`` or flat in ``search_params``): see ``search_rows``.  Hits of a grouped
+        search carry the group field in ``entity``, as pymilvus adds it to the output fields."""
         idx, score = self.search_rows(collection_name, data, filter=filter, limit=limit, search_params=search_params,
-                                      anns_field=anns_field, metric_type=metric_type, param=param)
-        return self.hits_from_rows(collection_name, idx, score, output_fields)
+                                      anns_field=anns_field, metric_type=metric_type, param=param, group_by_field=group_by_field,
+                                      group_size=group_size, strict_group_size=strict_group_size, offset=offset)
+        return self.hits_from_rows(collection_name, idx, score, output_fields, group_by_field=group_by_field)
+
+    @staticmethod
+    def _range_of(metric: str, search_params: Optional[dict], param: Optional[dict]):
+        """(radius, range_filter) of a request, None where absent: from search_params["params"], param["params"], flat search_params."""
+        out = []
+        for name in ("radius", "range_filter"):
+            v = None
+            for src in ((search_params or {}).get("params"), (param or {}).get("params"), search_params):
+                if isinstance(src, dict) and src.get(name) is not None:
+                    v = float(src[name])
+                    break
+            out.append(v)
+        radius, range_filter = out
+        if radius is not None and range_filter is not None and (range_filter >= radius if metric == "L2" else radius >= range_filter):
+            raise MilvusException(1100, f"range_filter({range_filter}) must be "
+                                        f"{'less' if metric == 'L2' else 'greater'} than radius({radius}) for {metric}")
+        return radius, range_filter
 
     def search_rows(self, collection_name: str, data, filter: Optional[str] = "", limit: int = 10, search_params: Optional[dict] = None,
-                    anns_field: Optional[str] = None, metric_type: Optional[str] = None, param: Optional[dict] = None, **_kw):
+                    anns_field: Optional[str] = None, metric_type: Optional[str] = None, param: Optional[dict] = None,
+                    group_by_field: Optional[str] = None, group_size: int = 1, strict_group_size: Optional[bool] = None,
+                    offset: int = 0, **_kw):
         """The arithmetic half of ``search``: -> (row index int64 [Q, k], cosine similarity fp32 [Q, k]) as numpy arrays, -1 = no hit
         (k = min(limit, live rows); k = 0 columns for an empty collection).  Row index == style id.  The data-parallel drivers shard
         THIS call over the ranks and all-gather its result (astts.parallel.sharded_search); ``hits_from_rows`` turns rows into the
-        pymilvus result shape wherever the records are written."""
+        pymilvus result shape wherever the records are written.
+
+        Selection controls (include/knn/astts_knn_grouped.h has the definition; a call that uses none of them takes the plain path):
+        ``radius`` / ``range_filter``: only rows with ``radius < score <= range_filter`` (COSINE / IP) or
+        ``range_filter <= distance < radius`` (L2) are hits.  ``group_by_field``: the ``limit`` groups whose best row is closest, in
+        that order, ``group_size`` rows of each -- columns ``g * group_size + j``, -1 where a group has fewer rows.
+        ``strict_group_size`` is accepted for compatibility: the result is ALWAYS the strict one (every returned group holds its
+        ``group_size`` closest eligible rows, or all it has), not Milvus' approximation.  ``offset`` skips the first ``offset`` groups
+        (hits without grouping): ``limit + offset`` are searched and sliced, ``(limit + offset) * group_size`` at most 1024.  The
+        bank-sharded merge of astts.parallel is not group-aware."""
         c = self._get(collection_name)
+        radius, range_filter = self._range_of(c.metric, search_params, param)
+        if int(offset) < 0 or int(group_size) < 1:
+            raise MilvusException(1100, f"offset {offset} / group_size {group_size} is invalid")
+        groups = c.group_codes(group_by_field) if group_by_field else None
+        selecting = groups is not None or int(offset) > 0 or radius is not None or range_filter is not None
         mask = None
         if filter:          # (the reference passes None: milvus/search_json.py:246-252)
             from ..milvus_filter import FilterSyntaxError, row_mask
@@ -398,8 +466,23 @@ class MilvusClient:
             return np.zeros((q.shape[0], 0), np.int64), np.zeros((q.shape[0], 0), np.float32)
         if limit < 1:
             raise MilvusException(1, f"limit {limit} is invalid")
-        k = min(int(limit), c.n_live)
         from .._lib import KNN_MAX_K
+        if selecting:       # limit + offset groups (hits) of group_size rows, sliced behind the search
+            gs = min(int(group_size), c.n_live) if groups is not None else 1
+            want = min(int(limit) + int(offset), c.n_live)
+            if want * gs > KNN_MAX_K:
+                raise MilvusException(1100, f"limit {limit} (+ offset {offset}, x group_size {gs}) is not supported by this build: at most "
+                                            f"{KNN_MAX_K} hits per query (collection holds {c.n_live} rows)")
+            codes, n_groups = groups if groups is not None else (None, None)
+            from .._lib import AsttsError
+            try:
+                idx, score = c.bank().search_grouped(q, want, gs, groups=codes, n_groups=n_groups, radius=radius,
+                                                     range_filter=range_filter, row_mask=mask)
+            except AsttsError as e:      # (the rounds ran out: never a partial answer)
+                raise MilvusException(1100, f"grouped search refused: {e}") from None
+            skip = min(int(offset), want) * gs
+            return np.asarray(idx, dtype=np.int64)[:, skip:], np.asarray(score, dtype=np.float32)[:, skip:]
+        k = min(int(limit), c.n_live)
         if k > KNN_MAX_K:
             # pymilvus accepts limit up to 16384; the reference asks for 1 or 3 (milvus/search_json.py:411,
             # milvus/search_embeddings.py:64).  Here: 32 certified hits per selection pass, at most 32 passes.
@@ -408,8 +491,10 @@ class MilvusClient:
         idx, score = c.bank().search(q, k, row_mask=mask) if mask is not None else c.bank().search(q, k)
         return np.asarray(idx, dtype=np.int64), np.asarray(score, dtype=np.float32)
 
-    def hits_from_rows(self, collection_name: str, idx, score, output_fields: Optional[Sequence[str]] = None) -> List[List[Dict[str, Any]]]:
-        """(row index [Q, k], similarity [Q, k]) -> ``list[Q]`` of ``list[<= k]`` of {'id', 'distance', 'entity', 'row'}."""
+    def hits_from_rows(self, collection_name: str, idx, score, output_fields: Optional[Sequence[str]] = None,
+                       group_by_field: Optional[str] = None) -> List[List[Dict[str, Any]]]:
+        """(row index [Q, k], similarity [Q, k]) -> ``list[Q]`` of ``list[<= k]`` of {'id', 'distance', 'entity', 'row'}.
+        ``group_by_field``: the field a grouped search grouped by; every hit carries it in ``entity`` (when the row has it)."""
         c = self._get(collection_name)
         idx, score = np.asarray(idx), np.asarray(score)
         out: List[List[Dict[str, Any]]] = []
@@ -424,6 +509,10 @@ class MilvusClient:
                     ent = {f: meta[f] for f in output_fields if f in meta}
                 else:
                     ent = {}
+                if group_by_field == c.pk_field:
+                    ent[group_by_field] = c.pks[row]
+                elif group_by_field in meta:
+                    ent[group_by_field] = meta[group_by_field]
                 hits.append({"id": c.pks[row], "distance": float(score[qi, j]), "entity": ent, "row": row})
             out.append(hits)
         return out

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, _lib_knn
+from . import _lib, _lib_knn, _lib_knn_grouped
 
 
 KNN_SCANS = ("DIRECT", "REGISTER", "GEMM", "GEMM_BLOCKS", "GEMM_N_FIRST")      # ASTTS_KNN_SCAN_*
@@ -91,6 +91,9 @@ class StyleBank:
         self._ws: Optional[torch.Tensor] = None
         self._ws_key: Tuple[int, int] = (0, 0)
         self._plans: dict = {}                       # (nq, k) -> (workspace tensor, aligned pointer, bytes)
+        self._gws: Optional[torch.Tensor] = None     # the grouped search's workspace and its plans per (nq, limit, group_size, n_groups)
+        self._gplans: dict = {}
+        self.last_rounds = 0                         # rounds the last grouped search took (rounds_host)
         self._search = lib.astts_knn_search
         self._refresh()
 
@@ -102,6 +105,7 @@ class StyleBank:
         self.n, self.live, self.capacity = int(n.value), int(live.value), int(cap.value)
         self.scan_plane_exact = bool(exact.value)
         self._plans = {}
+        self._gplans = {}
 
     # ---- mutation (each call synchronises the current stream, as the constructor does)
     def reserve(self, capacity: int) -> None:
@@ -242,6 +246,104 @@ class StyleBank:
         if row_mask is not None and not isinstance(row_mask, torch.Tensor):
             row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
         idx, sc = self.search_device(q.to(self.device), k, force_exact, row_mask=row_mask)
+        return idx.cpu().numpy(), sc.cpu().numpy()
+
+    # ---- grouped and ranged search (include/knn/astts_knn_grouped.h)
+    def search_grouped_device(self, queries: torch.Tensor, limit: int, group_size: int = 1, groups: Optional[torch.Tensor] = None,
+                              n_groups: Optional[int] = None, radius: Optional[float] = None, range_filter: Optional[float] = None,
+                              row_mask: Optional[torch.Tensor] = None, force_exact: bool = False, return_f64: bool = False,
+                              max_rounds: int = 0):
+        """The ``limit`` groups whose best row is closest, ``group_size`` rows of each, within the range: -> (idx int64, score fp32
+        ``[Q, limit * group_size]``) on the GPU (``return_f64``: and the fp64 scores), slot ``g * group_size + j`` = the j-th row of the
+        g-th group, -1 / -inf (+inf for L2) where a row or a group is missing.  Ids are exact with respect to the definition in
+        include/knn/astts_knn_grouped.h; the scores are bit for bit those of ``search_device``.
+
+        ``queries`` / ``row_mask`` / ``force_exact``: as in ``search_device``.  ``groups``: int32 ``[N]`` on this bank's GPU, the group
+        code of every row in ``[0, n_groups)`` (``n_groups``: default ``groups.max() + 1``, which synchronises); ``None``: every row is
+        its own group.  ``radius`` / ``range_filter``: COSINE / IP ``radius < score <= range_filter``, L2
+        ``range_filter <= distance < radius``.  Runs on the current stream and SYNCHRONISES it once per round (one round when the
+        first 32 hits settle every query; ``last_rounds`` tells how many it took; ``max_rounds`` 0 = 64, beyond it the call raises)."""
+        if queries.dim() != 2 or queries.shape[1] != self.d:
+            raise ValueError(f"queries must be [Q, {self.d}], got {tuple(queries.shape)}")
+        limit, group_size = int(limit), int(group_size)
+        if limit < 1 or group_size < 1 or limit * group_size > _lib.KNN_MAX_K:
+            raise ValueError(f"limit * group_size must be in 1..{_lib.KNN_MAX_K}, got {limit} x {group_size}")
+        slots = limit * group_size
+        q = queries
+        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
+            q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = int(q.shape[0])
+        out_idx = torch.empty((nq, slots), dtype=torch.int64, device=self.device)
+        out_score = torch.empty((nq, slots), dtype=torch.float32, device=self.device)
+        s64 = torch.empty((nq, slots), dtype=torch.float64, device=self.device) if return_f64 else None
+        self.last_rounds = 0
+        if nq == 0:
+            return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+        lib = _lib_knn_grouped.load()
+        with torch.cuda.device(self.device):
+            gptr, ng = None, 1
+            if groups is not None:
+                if groups.shape != (self.n,) or groups.dtype != torch.int32 or groups.device != self.device:
+                    raise ValueError(f"groups must be int32 [{self.n}] on {self.device}, got {groups.dtype} {tuple(groups.shape)} on {groups.device}")
+                groups = groups.contiguous()
+                ng = int(n_groups) if n_groups is not None else int(groups.max()) + 1
+                gptr = groups.data_ptr()
+            key = (nq, limit, group_size, ng if groups is not None else 0)
+            plan = self._gplans.get(key)
+            if plan is None:
+                need = int(lib.astts_knn_grouped_workspace_bytes(self._h, *key))
+                if need == 0:
+                    raise ValueError(f"invalid grouped search shape nq={nq} limit={limit} group_size={group_size} n_groups={ng} (n={self.n})")
+                if self._gws is None or self._gws.numel() < need + 256:
+                    self._gws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                    self._gplans = {}
+                base = self._gws.data_ptr()
+                aligned = (base + 255) // 256 * 256
+                plan = self._gplans[key] = (self._gws, aligned, self._gws.numel() - (aligned - base))
+            _, aligned, ws_bytes = plan
+            mptr, mstride = None, 0
+            if row_mask is not None:
+                m = row_mask.to(device=self.device)
+                m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
+                if m.shape == (self.n,):
+                    mstride = 0
+                elif m.shape == (nq, self.n):
+                    mstride = self.n
+                else:
+                    raise ValueError(f"row_mask must be [{self.n}] or [{nq}, {self.n}], got {tuple(m.shape)}")
+                mptr = m.data_ptr()
+            rad = None if radius is None else ctypes.c_double(float(radius))
+            rf = None if range_filter is None else ctypes.c_double(float(range_filter))
+            rounds = ctypes.c_int32()
+            rc = lib.astts_knn_search_grouped(self._h, q.data_ptr(), nq, limit, group_size, gptr, ng,
+                                              None if rad is None else ctypes.addressof(rad), None if rf is None else ctypes.addressof(rf),
+                                              out_idx.data_ptr(), out_score.data_ptr(), None if s64 is None else s64.data_ptr(),
+                                              mptr, mstride, aligned, ws_bytes, _lib.KNN_FORCE_EXACT if force_exact else 0, int(max_rounds),
+                                              ctypes.addressof(rounds), torch.cuda.current_stream(self.device).cuda_stream)
+            self.last_rounds = int(rounds.value)
+            if rc != 0:
+                _lib.check(rc)
+        return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+
+    def search_grouped(self, queries, limit: int, group_size: int = 1, groups=None, n_groups: Optional[int] = None,
+                       radius: Optional[float] = None, range_filter: Optional[float] = None, row_mask=None, force_exact: bool = False,
+                       max_rounds: int = 0):
+        """Host convenience of ``search_grouped_device``: accepts numpy / lists (``groups``: integer codes ``[N]``, checked to lie in
+        ``[0, n_groups)``), returns numpy (idx int64, score fp32 ``[Q, limit * group_size]``)."""
+        q = torch.as_tensor(np.asarray(queries, dtype=np.float32))
+        if q.dim() == 1:
+            q = q[None, :]
+        if groups is not None and not isinstance(groups, torch.Tensor):
+            g = np.ascontiguousarray(np.asarray(groups).reshape(-1).astype(np.int64))
+            if n_groups is None:
+                n_groups = int(g.max()) + 1 if g.size else 1
+            if g.size != self.n or (g.size and (g.min() < 0 or g.max() >= n_groups)):
+                raise ValueError(f"groups must be {self.n} codes in [0, {n_groups})")
+            groups = torch.from_numpy(g.astype(np.int32)).to(self.device)
+        if row_mask is not None and not isinstance(row_mask, torch.Tensor):
+            row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
+        idx, sc = self.search_grouped_device(q.to(self.device), limit, group_size, groups, n_groups, radius, range_filter, row_mask,
+                                             force_exact, max_rounds=max_rounds)
         return idx.cpu().numpy(), sc.cpu().numpy()
 
     def route(self, nq: int, k: int, masked: bool = False, aligned: bool = True):
