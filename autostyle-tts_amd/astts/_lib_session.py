@@ -1,6 +1,7 @@
-"""ctypes binding of the decode-session entry points of libastts.so (include/session/astts_lm_session.h).
+"""ctypes binding of the session entry points of libastts.so (include/session/astts_lm_session.h: decode sessions,
+include/session/astts_flow_session.h: flow sessions).
 
-The session calls live in libastts.so itself; their signatures are parsed from their own header exactly as astts/_lib.py parses
+The session calls live in libastts.so itself; their signatures are parsed from their own headers exactly as astts/_lib.py parses
 include/astts.h, and set on the library object that module loads.
 """
 from __future__ import annotations
@@ -10,16 +11,20 @@ import os
 
 from . import _lib
 
-HEADER_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "include", "session",
-                                            "astts_lm_session.h"))
+_DIR = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "include", "session"))
+HEADER_PATH = os.path.join(_DIR, "astts_lm_session.h")
+FLOW_HEADER_PATH = os.path.join(_DIR, "astts_flow_session.h")
 
 
 @functools.lru_cache(maxsize=None)
 def signatures() -> dict:
-    if not os.path.exists(HEADER_PATH):
-        raise _lib.AsttsLibraryMissing(f"{HEADER_PATH} not found: the ctypes signatures of the session calls are derived from this header")
-    with open(HEADER_PATH) as f:
-        return _lib.parse_prototypes(f.read())
+    sigs = {}
+    for path in (HEADER_PATH, FLOW_HEADER_PATH):
+        if not os.path.exists(path):
+            raise _lib.AsttsLibraryMissing(f"{path} not found: the ctypes signatures of the session calls are derived from this header")
+        with open(path) as f:
+            sigs.update(_lib.parse_prototypes(f.read()))
+    return sigs
 
 
 @functools.lru_cache(maxsize=None)

@@ -331,6 +331,21 @@ class FlowDecoder:
         x = (self.solve if self.use_engine else self.solve_ops)(z.clone(), mu, spk_e, cond)
         return x[:, tmp:].contiguous()
 
+    def session(self, t: int, slots: int = 4, rows_max: int = 32, stream=None) -> "FlowSession":
+        """A chain of estimator passes that up to ``slots`` batches of ``t`` frames (``rows_max`` rows together) share: see FlowSession."""
+        return FlowSession(self, t, slots, rows_max, stream)
+
+    def prepare(self, tokens, token_lens, prompt_mel, spk, z, mel_total: int):
+        """What ``decode`` computes before its solve (token encoder, speaker affine, prompt condition, the start noise's copy)
+        -> (x, mu, spk_e, cond, prompt frames): the arguments of ``solve`` / ``FlowSession.admit``; the mel is ``x[:, prompt frames:]``."""
+        b = tokens.shape[0]
+        mu = self.mu(tokens, token_lens, mel_total)
+        spk_e = ops.linear(torch.nn.functional.normalize(spk, dim=1), self.spk_aff)
+        tmp = prompt_mel.shape[1]
+        cond = torch.zeros((b, mel_total, self.cfg.mel), dtype=torch.float32, device=self.device)
+        cond[:, :tmp] = prompt_mel
+        return z.clone(), mu, spk_e, cond, tmp
+
     def decode_ragged(self, tokens: List[torch.Tensor], prompt_mels: List[torch.Tensor], spk: torch.Tensor,
                       zs: List[torch.Tensor]) -> List[torch.Tensor]:
         """Ragged batch: row i = (prompt + generated tokens [Ti], prompt mel [Tm_p_i, mel], noise z [mel_total_i, mel]).
@@ -355,3 +370,96 @@ class FlowDecoder:
         spk_e = ops.linear(torch.nn.functional.normalize(spk.to(dev), dim=1), self.spk_aff)
         x = (self.solve if self.use_engine else self.solve_ops)(x, mu, spk_e, cond, mel_lens)
         return [x[i, tmp[i]:mt[i]].contiguous() for i in range(b)]
+
+
+class FlowJob:
+    """One batch in a FlowSession: ``x`` [B, T, mel] is the mel (in place) once ``FlowSession.step`` has returned the job.  The job
+    keeps the tensors the session's kernels read until the batch's last step."""
+
+    def __init__(self, x, mu, spk_e, cond, lens, n_steps: int):
+        self.x, self.mu, self.spk_e, self.cond, self.lens = x, mu, spk_e, cond, lens
+        self.n_steps, self.next, self.slot = int(n_steps), 0, -1
+
+
+class FlowSession:
+    """A chain of estimator passes of the C++ solver that up to ``slots`` batches of the same frame count ``t`` share
+    (include/session/astts_flow_session.h): a batch admitted while others are being solved JOINS them, and every launch of a pass carries
+    the sequences of all of them, each batch at its own Euler step.  A batch's mel is bit-identical to ``FlowDecoder.solve`` of that
+    batch alone (tested).  All calls enqueue on ``stream`` (the stream current at construction by default) and none waits for the GPU;
+    they are not thread-safe: one thread drives a session."""
+
+    def __init__(self, flow: FlowDecoder, t: int, slots: int = 4, rows_max: int = 32, stream=None):
+        from .. import _lib_session
+        self.flow, self.t, self.slots, self.rows_max = flow, int(t), int(slots), int(rows_max)
+        self.stream = stream if stream is not None else torch.cuda.current_stream(flow.device)
+        self._lib = _lib_session.load()
+        self._tv, self._dv = flow._schedule()
+        eng = flow._engine()
+        need = int(self._lib.astts_flow_session_bytes(eng, self.t, self.slots, self.rows_max, len(self._tv)))
+        if need == 0:
+            raise ValueError(f"FlowSession: t={t} slots={slots} rows_max={rows_max} steps={len(self._tv)}")
+        with torch.cuda.stream(self.stream):
+            self._ws = torch.empty(need, dtype=torch.uint8, device=flow.device)
+        h = ctypes.c_void_p()
+        _lib.check(self._lib.astts_flow_session_create(eng, self.t, self.slots, self.rows_max, len(self._tv), self._ws.data_ptr(), need,
+                                                       _lib.stream_ptr(self.stream), ctypes.byref(h)))
+        self._h = h
+        self._ctx: List[Optional[FlowJob]] = [None] * 4       # per slot: the job of the batch that holds it
+
+    def close(self) -> None:
+        if self._h is not None:
+            h, self._h = self._h, None
+            _lib.check(self._lib.astts_flow_session_destroy(h))
+
+    def active(self) -> int:
+        return sum(c is not None for c in self._ctx)
+
+    def steps_left(self) -> List[int]:
+        return [c.n_steps - c.next for c in self._ctx if c is not None]
+
+    def can_admit(self, b: int, t: int) -> bool:
+        return int(self._lib.astts_flow_session_can_admit(self._h, int(b), int(t), len(self._tv))) >= 0
+
+    def state(self) -> List[int]:
+        """active-slot mask, rows in use, passes enqueued, batches those passes carried (summed), steps left of slots 0..3"""
+        out = (ctypes.c_int32 * 8)()
+        _lib.check(self._lib.astts_flow_session_state(self._h, out))
+        return list(out)
+
+    def admit(self, x: torch.Tensor, mu: torch.Tensor, spk_e: torch.Tensor, cond: torch.Tensor,
+              lens: Optional[torch.Tensor] = None) -> FlowJob:
+        """The arguments of ``FlowDecoder.solve``: ``x`` [B, T, mel] (noise) is solved in place."""
+        b, t, _ = x.shape
+        assert x.is_contiguous() and mu.is_contiguous() and cond.is_contiguous() and spk_e.is_contiguous()
+        assert x.dtype == mu.dtype == cond.dtype == spk_e.dtype == torch.float32
+        n = len(self._tv)
+        job = FlowJob(x, mu, spk_e, cond, lens, n)
+        slot = ctypes.c_int32(-1)
+        with torch.cuda.stream(self.stream):
+            _lib.check(self._lib.astts_flow_session_admit(self._h, x.data_ptr(), mu.data_ptr(), spk_e.data_ptr(), cond.data_ptr(),
+                                                          None if lens is None else lens.data_ptr(), b, t, n, (ctypes.c_float * n)(*self._tv),
+                                                          (ctypes.c_float * n)(*self._dv), self.flow.cfg.cfg_rate, ctypes.byref(slot)))
+        job.slot = int(slot.value)
+        self._ctx[job.slot] = job
+        return job
+
+    def step(self, k: int = 1) -> List[FlowJob]:
+        """Enqueue up to ``k`` estimator passes (with every batch's Euler update) over all admitted batches -> the jobs that ended."""
+        mask = ctypes.c_uint32(0)
+        k = int(k)
+        with torch.cuda.stream(self.stream):
+            _lib.check(self._lib.astts_flow_session_step(self._h, k, ctypes.byref(mask)))
+        done = []
+        for slot, c in enumerate(self._ctx):
+            if c is None:
+                continue
+            c.next = min(c.n_steps, c.next + k)
+            if mask.value >> slot & 1:
+                done.append(c)
+                self._ctx[slot] = None
+        return done
+
+    def run(self) -> None:
+        """Enqueue every remaining step of the admitted batches."""
+        while self.active():
+            self.step(max(self.steps_left()))

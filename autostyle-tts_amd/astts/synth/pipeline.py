@@ -203,6 +203,148 @@ class _JoinChain:
                     f.set_exception(e)
 
 
+class _JoinRender:
+    """The render stage of ``PipelinedSynth(render_join=True)``: the render stream, a FlowSession on it and the host thread that drives
+    it.  When a batch's tokens are ready the thread runs that batch's encoder (mu, speaker affine, prompt condition), admits it and
+    enqueues ONE Euler step at a time for everything admitted -- a batch joins between two steps, and every launch of an estimator pass
+    then carries the sequences of all admitted batches -- staying at most ``AHEAD`` steps ahead of the GPU (it waits for the event of
+    the step before last on the host, here, never in the C call); the vocoder runs per batch when its solve ends.  A batch whose frame
+    count differs from a busy session's, or that does not fit its rows, is rendered alone as without the session."""
+
+    SLOTS, ROWS_MAX, AHEAD = 4, 32, 2
+
+    def __init__(self, engine, stream):
+        self.eng, self.device, self.stream = engine, engine.device, stream
+        self.session = None                 # created / replaced by the worker's thread only
+        self._cv = threading.Condition()
+        self._waiting = []                  # items handed over and not admitted yet, oldest first
+        self._stop = False
+        self._dead = None
+        self._thread = None
+        self.passes = self.carried = 0      # estimator passes enqueued by sessions this worker has closed, and the batches they carried
+        self.gate = threading.Event()       # cleared: the thread admits nothing and enqueues nothing (tests: queue the batches, then open)
+        self.gate.set()
+
+    def submit(self, item, ready) -> None:
+        """``item["fut"]`` is set (its LM stage is launched); ``ready``: the event on the caller's stream behind which the item's render
+        inputs exist.  ``item["rfut"]`` resolves to (toks, mel, wav) once the batch's vocoder is enqueued."""
+        item["rfut"], item["ready"] = Future(), ready
+        with self._cv:
+            if self._dead is not None:
+                raise RuntimeError(f"render worker stopped: {self._dead!r}") from self._dead
+            self._waiting.append(item)
+            if self._thread is None:
+                self._thread = threading.Thread(target=self._run, name="astts-join-render", daemon=True)
+                self._thread.start()
+        item["fut"].add_done_callback(self._wake)
+
+    def _wake(self, _fut=None) -> None:
+        with self._cv:
+            self._cv.notify()
+
+    def stats(self):
+        """(estimator passes enqueued, batches they carried summed): carried / passes = batches per shared pass"""
+        s = self.session.state() if self.session is not None else [0] * 8
+        return self.passes + s[2], self.carried + s[3]
+
+    def close(self) -> None:
+        with self._cv:
+            self._stop = True
+            self._cv.notify()
+        self.gate.set()
+        if self._thread is not None:
+            self._thread.join()
+            self._thread = None
+        self._drop_session()
+
+    def _drop_session(self) -> None:
+        if self.session is not None:
+            self.passes, self.carried = self.stats()
+            self.session.close()
+            self.session = None
+
+    def _take_ready(self):
+        """The oldest waiting batch whose decode is enqueued to its end -- and, while the session is solving other batches, whose tokens
+        are there already: the render stream has to wait for the tokens' event, and everything admitted would wait with it."""
+        busy = self.session is not None and self.session.active() > 0
+        with self._cv:
+            for i, item in enumerate(self._waiting):
+                fut = item["fut"]
+                if fut.done() and (not busy or fut.exception() is not None or fut.result()[1].query()):
+                    return self._waiting.pop(i)
+        return None
+
+    def _begin(self, item, jobs) -> None:
+        """The batch's tokens are ready: encoder + admission (or the whole render, alone, when the session cannot take it)."""
+        eng, sr = self.eng, self.stream
+        try:
+            parts, ev = item["fut"].result()
+        except Exception as e:      # noqa: BLE001  (the batch's decode failed: that is this batch's result)
+            item["rfut"].set_exception(e)
+            return
+        toks = parts[item["k"]]
+        sr.wait_event(ev)
+        sr.wait_event(item["ready"])
+        toks.record_stream(sr)
+        record_streams(item["render"], sr)      # the caller's tensors, read on the render stream
+        ptok, pmel, spk, z, phase0, noise = item["render"]
+        b = int(toks.shape[0])
+        mel_total = int(pmel.shape[1]) + eng.cfg.mel_frames_for_tokens(toks.shape[1])
+        idle = self.session is None or not self.session.active()
+        if idle and b <= self.ROWS_MAX and (self.session is None or self.session.t != mel_total):
+            self._drop_session()
+            self.session = eng.flow.session(mel_total, self.SLOTS, self.ROWS_MAX, sr)
+        if not eng.flow.use_engine or self.session is None or not self.session.can_admit(b, mel_total):
+            mel, wav = eng.tts_render(toks, *item["render"])
+            item["rfut"].set_result((toks, mel, wav))
+            return
+        all_tok = torch.cat([ptok.to(torch.int32), toks], dim=1)
+        tok_lens = torch.full((b,), all_tok.shape[1], dtype=torch.int32, device=self.device)
+        x, mu, spk_e, cond, tmp = eng.flow.prepare(all_tok, tok_lens, pmel, spk, z, mel_total)
+        jobs[id(self.session.admit(x, mu, spk_e, cond))] = (item, toks, tmp)
+
+    def _run(self):
+        ahead = deque()
+        jobs = {}
+        item = None
+        try:
+            with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+                while True:
+                    self.gate.wait()
+                    with self._cv:
+                        while not self._stop and not (self.session is not None and self.session.active()) and \
+                                not any(w["fut"].done() for w in self._waiting):
+                            self._cv.wait()
+                        if self._stop:
+                            return
+                    while True:
+                        item = self._take_ready()
+                        if item is None:
+                            break
+                        self._begin(item, jobs)
+                        item = None
+                    if self.session is None or not self.session.active():
+                        continue
+                    for job in self.session.step(1):
+                        it, toks, tmp = jobs.pop(id(job))
+                        mel = job.x[:, tmp:].contiguous()
+                        wav = self.eng.hift.forward(mel, it["render"][4], it["render"][5])
+                        it["rfut"].set_result((toks, mel, wav))
+                    mark = torch.cuda.Event()
+                    mark.record(self.stream)
+                    ahead.append(mark)
+                    if len(ahead) > self.AHEAD:
+                        ahead.popleft().synchronize()
+        except BaseException as e:      # noqa: BLE001  (handed to whoever waits for a batch this worker holds; later submits raise)
+            with self._cv:
+                self._dead = e
+                held = [w for w in self._waiting] + [j[0] for j in jobs.values()] + ([item] if item is not None else [])
+                self._waiting.clear()
+            for it in held:
+                if not it["rfut"].done():
+                    it["rfut"].set_exception(e)
+
+
 class PipelinedSynth:
     """Software pipeline over consecutive (independent) batches on several HIP streams of one GPU.
 
@@ -229,14 +371,23 @@ class PipelinedSynth:
     Footprint: every chain keeps a daemon host thread and its session's cache arena -- layers * 2 * window * 16 rows * 4 d bytes,
     0.94 GB per chain at CosyVoice-300M widths and windows of up to 512 keys, 2.8 GB at three chains -- until ``close()`` is called
     (``autotune`` closes the pipelines it does not return; the one it returns is the caller's to close).  A chain whose arena is too
-    short for a batch is given a longer one when it holds no batch."""
+    short for a batch is given a longer one when it holds no batch.
+
+    ``render_join`` (with one render stream): the render stage is a flow SESSION (FlowSession) driven by a host thread of its own
+    (_JoinRender).  A batch whose tokens are ready joins the Euler solve that is running -- the launches of an estimator pass then
+    carry the sequences of up to four batches, each at its own step -- instead of queueing behind it; same bits as rendering each
+    batch alone (tested).  ``submit`` then returns a batch once the worker is through with it, which may be later than without
+    ``render_join`` (more ``None`` returns, more results from ``drain``); every batch is still returned exactly once.  Footprint: one
+    more daemon thread and the session's workspace (that of a 64-sequence solve) until ``close()``."""
 
     JOIN_QUANTUM = 16        # token steps a chain's thread enqueues between two looks at its queue of batches that want to join
     JOIN_AHEAD = 2           # ... and the ranges it keeps enqueued ahead of the GPU: a batch can only join what is not enqueued yet
+    # whether ``autotune`` also tries the joined render (``render_join``) beside the joining chains; ASTTS_PIPE_RENDER_JOIN=0 / 1 overrides
+    AUTOTUNE_RENDER_JOIN = os.environ.get("ASTTS_PIPE_RENDER_JOIN", "1") != "0"
 
     def __init__(self, engine, lm_depth: int = 2, lm_priority: int = -1, render_priority: int = 0, streams=None,
                  cobatch: int = 1, render_depth: int = 1, pipe_classes=None, front_prefill: Optional[bool] = None,
-                 stagger_ms: Optional[float] = None, wide_lm: bool = False, join: bool = False):
+                 stagger_ms: Optional[float] = None, wide_lm: bool = False, join: bool = False, render_join: bool = False):
         self.eng = engine
         self.depth = max(1, int(lm_depth))
         # ``render_depth`` > 1: the flow + vocoder stages of consecutive batches alternate between that many streams.  One
@@ -286,12 +437,18 @@ class PipelinedSynth:
         lm_ = engine.lm
         self._chains = [_JoinChain(lm_, dev, self.s_lm[c], c, self.JOIN_QUANTUM, self.JOIN_AHEAD, lm_.body.center)
                         for c in range(self.depth)] if self.join else []
+        # ``render_join``: the render stage is a flow SESSION driven by a thread of its own (_JoinRender): batches whose tokens are ready
+        # join the Euler solve that is running instead of queueing behind it
+        self.render_join = bool(render_join) and rd == 1
+        self._renderer = _JoinRender(engine, self.s_render) if self.render_join else None
 
     def close(self) -> None:
         """Stop the chains' threads and free their sessions (``join``); the pipeline must be drained."""
         for ch in self._chains:
             ch.close()
         self._chains = []
+        if self._renderer is not None:
+            self._renderer.close()
         self._pool.shutdown(wait=True)
 
     @classmethod
@@ -318,13 +475,16 @@ class PipelinedSynth:
                 if join and (cfg_[1] != 1 or wide_lm):
                     continue
                 tried.append(tuple(cfg_) + ("join",) if join else cfg_)
+                # ... and the joining chains with the joined render (one render stream: the session is that stream's)
+                if join and cls.AUTOTUNE_RENDER_JOIN and len(cfg_) < 3:
+                    tried.append(tuple(cfg_) + ("join", "render_join"))
         for cfg_ in tried:
-            join = cfg_[-1] == "join"
-            depth, cob, rdep = (tuple(cfg_[:-1] if join else cfg_) + (1,))[:3]
+            join, rjoin = "join" in cfg_, "render_join" in cfg_
+            depth, cob, rdep = (tuple(c for c in cfg_ if not isinstance(c, str)) + (1,))[:3]
             for _ in range(trials):
                 lm_prio = int(os.environ.get("ASTTS_PIPE_LM_PRIORITY", "0"))      # experiments: -1 = high-priority decode streams
                 pipe = cls(engine, lm_depth=depth, lm_priority=lm_prio, render_priority=0, cobatch=cob, render_depth=rdep,
-                           pipe_classes=classes if rdep == 1 and lm_prio == 0 else None, wide_lm=wide_lm, join=join)
+                           pipe_classes=classes if rdep == 1 and lm_prio == 0 else None, wide_lm=wide_lm, join=join, render_join=rjoin)
                 with torch.cuda.stream(pipe.front_stream):
                     for _ in range((depth + 1) * cob):
                         if front is not None:
@@ -341,7 +501,7 @@ class PipelinedSynth:
                     torch.cuda.synchronize(engine.device)
                 dt = (time.perf_counter() - t0) / steps
                 if verbose:
-                    print(f"PipelinedSynth.autotune: depth {depth} cobatch {cob} render streams {rdep} join {join}: {dt * 1e3:.1f} ms/batch", flush=True)
+                    print(f"PipelinedSynth.autotune: depth {depth} cobatch {cob} render streams {rdep} join {join} render join {rjoin}: {dt * 1e3:.1f} ms/batch", flush=True)
                 if dt < best_dt:
                     best, best_dt = pipe, dt
                 if not per_cfg or per_cfg[-1][2] != cfg_:
@@ -410,8 +570,18 @@ class PipelinedSynth:
         fut = self._pool.submit(lm_stage)
         for k, g in enumerate(group):
             g["fut"], g["k"] = fut, k
+            self._to_renderer(g)
+
+    def _to_renderer(self, item) -> None:
+        """``render_join``: the batch's LM stage is launched -- the render worker takes it from here."""
+        if self._renderer is not None:
+            self._renderer.submit(item, item["ready"])
 
     def _render(self, item):
+        if self._renderer is not None:      # enqueued by the render worker: wait (on the host) until it has enqueued this batch's vocoder
+            out = item["rfut"].result()
+            record_streams(out, torch.cuda.current_stream(self.eng.device))
+            return out
         parts, ev = item["fut"].result()
         toks = parts[item["k"]]
         cur = torch.cuda.current_stream(self.eng.device)
@@ -431,11 +601,21 @@ class PipelinedSynth:
     def submit(self, text, text_lens, lm_spk, lm_prompt_tokens, n_tokens, uniforms, flow_prompt_tokens, flow_prompt_mel,
                flow_spk, z, phase0, noise):
         cur = torch.cuda.current_stream(self.eng.device)
-        for sr in self.s_renders:
-            sr.wait_stream(cur)
         item = {"lm": LmArgs(text, text_lens, lm_spk, lm_prompt_tokens, n_tokens, uniforms),
                 "render": (flow_prompt_tokens, flow_prompt_mel, flow_spk, z, phase0, noise), "fut": None, "k": 0}
+        if self._renderer is None:
+            for sr in self.s_renders:
+                sr.wait_stream(cur)
+        else:       # the worker enqueues on the render stream from its own thread: it orders the stream behind this event itself
+            item["ready"] = torch.cuda.Event()
+            item["ready"].record(cur)
         if self.join and self._join_submit(item):
+            if self._renderer is not None:
+                # the render worker takes batches as their tokens become ready: submit hands over the oldest batch only once the worker
+                # is through with it, and waits for it only when more batches are in flight than chains and session hold together
+                rfut = self._fifo[0].get("rfut")
+                done = rfut is not None and (rfut.done() or len(self._fifo) > 2 * self.depth + _JoinRender.SLOTS)
+                return self._render(self._fifo.popleft()) if done else None
             return self._render(self._fifo.popleft()) if len(self._fifo) > 2 * self.depth else None
         if self._pending and not self._compatible(self._pending[0]["lm"], item["lm"]):
             self._launch_group()
@@ -477,6 +657,7 @@ class PipelinedSynth:
             raise RuntimeError("PipelinedSynth: no decode chain can take the batch although none holds one")
         self._fifo.append(item)
         item["fut"] = chain.submit(state, lm_args)
+        self._to_renderer(item)
         return True
 
     def _compatible(self, a: LmArgs, b: LmArgs) -> bool:

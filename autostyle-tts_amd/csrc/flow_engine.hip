@@ -13,6 +13,8 @@
 // fp32; tensors consumed only by MFMA operands (GroupNorm-1 / LayerNorm / qkv / attention / GELU
 // outputs) are fp16.
 #include "common.h"
+#include "flow_session.h"
+#include "../../include/session/astts_flow_session.h"
 
 #include <vector>
 
@@ -154,20 +156,63 @@ size_t carve(const astts_flow* h, int b, int t, char* base, Buffers* B) {
     return o;
 }
 
+// one batch's share of an estimator pass: its own tensors, its sequences [seq0, seq0 + 2 b) of the pass, its Euler step
+struct Seg {
+    float* x;
+    const float *mu, *spk, *cond;
+    int seq0, b;
+    float dt, cfg_rate;
+};
+
 struct Ctx {
     const astts_flow* h;
     Buffers B;
-    int b2, T;
+    int b2, T;          // b2: sequences of the pass (all batches')
     bool full;
     astts_stream_t st;
+    const Seg* seg;     // the batches of the pass; astts_flow_solve: one
+    int n_seg;
 
-    int gemm(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
-             int t_in, int t_out, int stride, int pad, int act) const {
+    int gemm1(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
+              int t_in, int t_out, int stride, int pad, int act) const {
         return astts_op_gemm(x, x16, w.w, w.bias, residual, nullptr, out, out16, m, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
                              residual ? w.n : 0, t_in, t_out, stride, 1, pad, act, 1.0f, 0.1f, nullptr, st);
     }
+    // a convolution over all sequences ([b2, t_in, cin] -> [b2, t_out, n]).  launch_gemm plans kernel and tile from the TOTAL row count
+    // (gemm_plan.h), so a joined pass issues it once per batch over the batch's own rows: the launch that batch gets alone.
+    int gemm(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
+             int t_in, int t_out, int stride, int pad, int act) const {
+        if (n_seg == 1) return gemm1(x, x16, w, residual, out, out16, m, t_in, t_out, stride, pad, act);
+        for (int i = 0; i < n_seg; ++i) {
+            const int64_t s0 = seg[i].seq0, nb = 2 * (int64_t)seg[i].b;
+            RUN(gemm1((const char*)x + s0 * t_in * w.cin * (x16 ? 2 : 4), x16, w, residual ? residual + s0 * t_out * w.n : nullptr,
+                      (char*)out + s0 * t_out * w.n * (out16 ? 2 : 4), out16, nb * t_out, t_in, t_out, stride, pad, act));
+        }
+        return ASTTS_OK;
+    }
     int linear(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m, int act) const {
-        return gemm(x, x16, w, residual, out, out16, m, (int)m, (int)m, 1, 0, act);
+        return gemm1(x, x16, w, residual, out, out16, m, (int)m, (int)m, 1, 0, act);
+    }
+    // a projection of the rows of all sequences ([b2 * t, cin] -> [b2 * t, n]): per batch in a joined pass, as gemm()
+    int linear_seq(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int t, int act) const {
+        if (n_seg == 1) return linear(x, x16, w, residual, out, out16, (int64_t)b2 * t, act);
+        for (int i = 0; i < n_seg; ++i) {
+            const int64_t r0 = (int64_t)seg[i].seq0 * t, m = 2 * (int64_t)seg[i].b * t;
+            RUN(linear((const char*)x + r0 * w.cin * (x16 ? 2 : 4), x16, w, residual ? residual + r0 * w.n : nullptr,
+                       (char*)out + r0 * w.n * (out16 ? 2 : 4), out16, m, act));
+        }
+        return ASTTS_OK;
+    }
+    // GroupNorm (+ time projection, Mish) of all sequences: astts_op_groupnorm sizes its grid by the sequence count, so per batch too
+    int gnorm(const float* x, const int* lens, const float* gw, const float* gb, const float* add_bc, void* y, int y16, int t) const {
+        const int C = h->cfg.channels, G = h->cfg.groups;
+        for (int i = 0; i < n_seg; ++i) {
+            const int64_t s0 = n_seg == 1 ? 0 : seg[i].seq0;
+            const int nb = n_seg == 1 ? b2 : 2 * seg[i].b;
+            RUN(astts_op_groupnorm(x + s0 * t * C, lens + s0, gw, gb, add_bc ? add_bc + s0 * C : nullptr, (char*)y + s0 * t * C * (y16 ? 2 : 4),
+                                   y16, nb, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
+        }
+        return ASTTS_OK;
     }
     int mask(float* x, const int* lens, int t, int c) const {
         if (full) return ASTTS_OK;
@@ -179,7 +224,7 @@ struct Ctx {
     // `next_w` / `next_bytes`: the weight image the launch after this block reads first (its first transformer block's q|k|v image)
     int resnet(const astts_flow_resnet_t& r, const float* tproj, const float* x, const int* lens, int t, float* out,
                const void* next_w = nullptr, uint32_t next_bytes = 0) const {
-        const int C = h->cfg.channels, G = h->cfg.groups;
+        const int G = h->cfg.groups;
         const int64_t rows = (int64_t)b2 * t;
         if (r.c1_frag && r.c2_frag && r.res_frag && astts_op_resnet_conv_supported(r.c1.cin, r.c1.n, G, r.c1.taps) &&
             astts_op_resnet_conv_supported(r.c2.cin, r.c2.n, G, r.c2.taps) && astts_op_resnet_conv_supported(r.res.cin, r.res.n, G, r.res.taps)) {
@@ -194,9 +239,9 @@ struct Ctx {
                                         nullptr, lens, b2, t, r.res.cin, r.res.taps, 1e-5f, next_w, next_bytes, st);
         }
         RUN(gemm(x, 0, r.c1, nullptr, B.r1, 0, rows, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(astts_op_groupnorm(B.r1, lens, r.g1_w, r.g1_b, tproj, B.r1h, 1, b2, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
+        RUN(gnorm(B.r1, lens, r.g1_w, r.g1_b, tproj, B.r1h, 1, t));
         RUN(gemm(B.r1h, 1, r.c2, nullptr, B.r2, 0, rows, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(astts_op_groupnorm(B.r2, lens, r.g2_w, r.g2_b, nullptr, B.r3, 0, b2, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
+        RUN(gnorm(B.r2, lens, r.g2_w, r.g2_b, nullptr, B.r3, 0, t));
         return gemm(x, 0, r.res, B.r3, out, 0, rows, t, t, 1, 0, ASTTS_ACT_NONE);     // res_conv(x) + h
     }
 
@@ -218,23 +263,37 @@ struct Ctx {
                                         (w.wo_frag && w.w1_frag && w.w2_frag) ? 3 : 0, st));
         } else {
             RUN(astts_op_layernorm(p, w.n1_w, w.n1_b, B.n16, 1, rows, C, C, C, 1e-5f, 0.0f, st));
-            RUN(linear(B.n16, 1, w.qkv, nullptr, B.qkv16, 1, rows, ASTTS_ACT_NONE));
+            RUN(linear_seq(B.n16, 1, w.qkv, nullptr, B.qkv16, 1, t, ASTTS_ACT_NONE));
             RUN(astts_op_attn_mha(B.qkv16, B.qkv16 + hd, B.qkv16 + 2 * hd, 1, lens, B.a16, 1, b2, heads, t, 3 * hd, 3 * hd, hd,
                                   0.125f, st));
         }
         const bool ffn = w.w1_frag && w.w2_frag && astts_op_tfm_ffn_fused_supported(C, w.w1.n);
         // output projection + residual + LayerNorm + W1 + GELU + W2 + residual in one launch (in place on p); faster than the
         // separate projection at every row count measured (5 504: 20.2 vs 26.8 us, 11 008: 36.6 vs 45.0, 44 032: 116 vs 128)
-        if (ffn && w.wo_frag && (hd == 256 || hd == 512))
-            return astts_op_tfm_ffn_fused(p, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, B.a16, w.wo_frag,
-                                          w.wo.bias, hd, next_w, next_bytes, st);
-        RUN(linear(B.a16, 1, w.wo, p, q, 0, rows, ASTTS_ACT_NONE));
-        if (ffn)      // LayerNorm + W1 + GELU + W2 + residual: one launch
-            return astts_op_tfm_ffn_fused(q, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, nullptr, nullptr, nullptr, 0, nullptr, 0,
-                                          st);
+        // tfm_ffn_fused sums the hidden chunks in an order rotated by the workgroup's index (a 32-row tile starts at chunk
+        // (tile / 8) % chunks): a row's bits depend on where its tile lies in the launch.  A joined pass therefore issues it per batch,
+        // over the batch's own rows from tile 0 -- the launch that batch gets alone.
+        if (ffn && w.wo_frag && (hd == 256 || hd == 512)) {
+            for (int i = 0; i < n_seg; ++i) {
+                const int64_t r0 = n_seg == 1 ? 0 : (int64_t)seg[i].seq0 * t, m = n_seg == 1 ? rows : 2 * (int64_t)seg[i].b * t;
+                const bool last = i + 1 == n_seg;
+                RUN(astts_op_tfm_ffn_fused(p + r0 * C, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p + r0 * C, m, C, w.w1.n, 1e-5f, B.a16 + r0 * hd,
+                                           w.wo_frag, w.wo.bias, hd, last ? next_w : nullptr, last ? next_bytes : 0u, st));
+            }
+            return ASTTS_OK;
+        }
+        RUN(linear_seq(B.a16, 1, w.wo, p, q, 0, t, ASTTS_ACT_NONE));
+        if (ffn) {    // LayerNorm + W1 + GELU + W2 + residual: one launch
+            for (int i = 0; i < n_seg; ++i) {
+                const int64_t r0 = n_seg == 1 ? 0 : (int64_t)seg[i].seq0 * t, m = n_seg == 1 ? rows : 2 * (int64_t)seg[i].b * t;
+                RUN(astts_op_tfm_ffn_fused(q + r0 * C, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p + r0 * C, m, C, w.w1.n, 1e-5f, nullptr, nullptr,
+                                           nullptr, 0, nullptr, 0, st));
+            }
+            return ASTTS_OK;
+        }
         RUN(astts_op_layernorm(q, w.n3_w, w.n3_b, B.n16, 1, rows, C, C, C, 1e-5f, 0.0f, st));
-        RUN(linear(B.n16, 1, w.w1, nullptr, B.f16, 1, rows, ASTTS_ACT_GELU));
-        return linear(B.f16, 1, w.w2, q, p, 0, rows, ASTTS_ACT_NONE);
+        RUN(linear_seq(B.n16, 1, w.w1, nullptr, B.f16, 1, t, ASTTS_ACT_GELU));
+        return linear_seq(B.f16, 1, w.w2, q, p, 0, t, ASTTS_ACT_NONE);
     }
 };
 
@@ -283,56 +342,58 @@ size_t astts_flow_workspace_bytes(const astts_flow_t* h, int32_t b, int32_t t) {
     return carve(h, b, t, nullptr, nullptr);
 }
 
-int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* spk, const float* cond, const int32_t* lens,
-                     int32_t b, int32_t t, int32_t n_steps, const float* t_host, const float* dt_host, float cfg_rate,
-                     void* workspace, size_t workspace_bytes, astts_stream_t stream) {
-    ASTTS_REQUIRE(h && x && mu && spk && cond && t_host && dt_host && workspace, ASTTS_ERR_INVALID, "astts_flow_solve: null argument");
-    ASTTS_REQUIRE(b >= 1 && t >= 2 && n_steps >= 1, ASTTS_ERR_INVALID, "astts_flow_solve: b=%d t=%d n_steps=%d", b, t, n_steps);
-    ASTTS_REQUIRE(workspace_bytes >= astts_flow_workspace_bytes(h, b, t) && ((uintptr_t)workspace & 255) == 0,
-                  ASTTS_ERR_WORKSPACE, "astts_flow_solve: workspace too small or misaligned");
+}  // extern "C"
+
+namespace {
+
+// where the time path of one batch lives: the rows of `steps` Euler steps x its 2 b sequences
+struct TimeBufs {
+    float *tv, *temb0, *temb1, *temb2, *tproj;
+};
+
+// The time path of `steps` Euler steps of one batch of b2 sequences, hoisted out of the dependent chain (it depends on the schedule
+// only): time embedding -> MLP -> Mish (every ResnetBlock1D applies Mish before its own projection) for all steps x b2 rows in one
+// pass, then ONE projection GEMM per ResNet block over all steps: ~20 launches per solve instead of 21 per step.
+// -> T.tproj [ResNet block][steps * b2][C]
+int time_path(const Ctx& k, const TimeBufs& T, const float* t_host, int steps, int b2) {
+    const astts_flow* h = k.h;
     const astts_flow_config_t& c = h->cfg;
-    hipStream_t st = (hipStream_t)stream;
-    Ctx k;
-    k.h = h;
-    k.b2 = 2 * b;
-    k.T = t;
-    k.full = lens == nullptr;
-    k.st = stream;
-    carve(h, b, t, (char*)workspace, &k.B);
+    hipStream_t st = (hipStream_t)k.st;
+    const int64_t trows = (int64_t)steps * b2;
+    for (int j = 0; j < steps; ++j) {
+        hipLaunchKernelGGL(flow_fill_time, dim3((b2 + 63) / 64), dim3(64), 0, st, T.tv + (size_t)j * b2, t_host[j], b2);
+        ASTTS_CHECK_LAUNCH();
+    }
+    RUN(astts_op_time_embedding(T.tv, T.temb0, (int)trows, c.time_in, 1000.0f, k.st));
+    RUN(k.linear(T.temb0, 0, c.t1, nullptr, T.temb1, 0, trows, ASTTS_ACT_SILU));
+    RUN(k.linear(T.temb1, 0, c.t2, nullptr, T.temb2, 0, trows, ASTTS_ACT_NONE));
+    RUN(astts_op_elementwise(ASTTS_EL_MISH, T.temb2, nullptr, nullptr, nullptr, T.temb2, trows * c.time_dim, 1, c.time_dim, 0.0f, 0.0f, k.st));
+    size_t rj = 0;
+    for (const std::vector<astts_flow::Block>* grp : {&h->down, &h->mid, &h->up})
+        for (const astts_flow::Block& blk : *grp)
+            RUN(k.linear(T.temb2, 0, blk.res.mlp, nullptr, T.tproj + (rj++) * (size_t)trows * c.channels, 0, trows, ASTTS_ACT_NONE));
+    return ASTTS_OK;
+}
+
+// One estimator pass over the k.b2 sequences of k.seg[0 .. k.n_seg), then every batch's own guidance + Euler update.
+// `tproj` + i * tproj_stride: the [b2, C] time projections of ResNet block i (down, mid, up order) for this pass;
+// `lens_full` / `lens_half` [b2]: the sequences' lengths at both time resolutions.
+int estimator_pass(const Ctx& k, const float* tproj, size_t tproj_stride, const int* lens_full, const int* lens_half) {
+    const astts_flow* h = k.h;
+    const astts_flow_config_t& c = h->cfg;
+    hipStream_t st = (hipStream_t)k.st;
     const Buffers& B = k.B;
-    const int b2 = k.b2, C = c.channels, mel = c.mel;
+    const int b2 = k.b2, t = k.T, C = c.channels, mel = c.mel;
     const int t_half = (t - 1) / 2 + 1;     // conv k=3, stride 2, pad 1
-
-    hipLaunchKernelGGL(flow_fill_lens, dim3((b2 + 63) / 64), dim3(64), 0, st, lens, B.lens_full, B.lens_half, b, t);
-    ASTTS_CHECK_LAUNCH();
-
-    // ---- the time path of every Euler step, hoisted out of the dependent chain (it depends on the schedule only): time
-    // embedding -> MLP -> Mish (every ResnetBlock1D applies Mish before its own projection) for all n_steps x 2B rows in one
-    // pass, then ONE projection GEMM per ResNet block over all steps: ~20 launches per solve instead of 21 per step.
-    // Solves with more than FLOW_MAX_STEPS steps evaluate it chunk by chunk (the workspace holds FLOW_MAX_STEPS steps).
-    for (int s = 0; s < n_steps; ++s) {
-      const int s0 = s - s % FLOW_MAX_STEPS, sl = s - s0;
-      const int64_t trows = (int64_t)(n_steps - s0 < FLOW_MAX_STEPS ? n_steps - s0 : FLOW_MAX_STEPS) * b2;
-      if (sl == 0) {
-        for (int j = 0; j < (int)(trows / b2); ++j) {
-            hipLaunchKernelGGL(flow_fill_time, dim3((b2 + 63) / 64), dim3(64), 0, st, B.tv + (size_t)j * b2, t_host[s0 + j], b2);
-            ASTTS_CHECK_LAUNCH();
-        }
-        RUN(astts_op_time_embedding(B.tv, B.temb0, (int)trows, c.time_in, 1000.0f, st));
-        RUN(k.linear(B.temb0, 0, c.t1, nullptr, B.temb1, 0, trows, ASTTS_ACT_SILU));
-        RUN(k.linear(B.temb1, 0, c.t2, nullptr, B.temb2, 0, trows, ASTTS_ACT_NONE));
-        RUN(astts_op_elementwise(ASTTS_EL_MISH, B.temb2, nullptr, nullptr, nullptr, B.temb2, trows * c.time_dim, 1, c.time_dim, 0.0f, 0.0f, st));
-        size_t rj = 0;
-        for (const std::vector<astts_flow::Block>* grp : {&h->down, &h->mid, &h->up})
-            for (const astts_flow::Block& blk : *grp)
-                RUN(k.linear(B.temb2, 0, blk.res.mlp, nullptr, B.tproj + (rj++) * (size_t)trows * C, 0, trows, ASTTS_ACT_NONE));
-      }
       {
         size_t ri = 0;      // ResNet block counter of this estimator pass (down, mid, up order: the order of the table above)
-        auto tproj_of = [&]() { return B.tproj + ((ri++) * (size_t)trows + (size_t)sl * b2) * C; };
-        hipLaunchKernelGGL(flow_pack_input, dim3(grid_for((int64_t)b2 * t * 4 * mel)), dim3(256), 0, st, x, mu, spk, cond,
-                           B.lens_full, B.xin, b, t, mel);
-        ASTTS_CHECK_LAUNCH();
+        auto tproj_of = [&]() { return tproj + (ri++) * tproj_stride; };
+        for (int i = 0; i < k.n_seg; ++i) {
+            const Seg& g = k.seg[i];
+            hipLaunchKernelGGL(flow_pack_input, dim3(grid_for((int64_t)2 * g.b * t * 4 * mel)), dim3(256), 0, st, g.x, g.mu, g.spk, g.cond,
+                               lens_full + g.seq0, B.xin + (size_t)g.seq0 * t * 4 * mel, g.b, t, mel);
+            ASTTS_CHECK_LAUNCH();
+        }
 
         // buffer pool: cur / other ping-pong for the residual stream, the rest become skips
         float* pool[6];
@@ -347,7 +408,7 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
         int n_skips = 0;
         const float* block_in = B.xin;
         int tt = t;
-        const int* L = B.lens_full;
+        const int* L = lens_full;
 
         const uint32_t qkv_bytes = 3u * (uint32_t)c.heads * 64u * (uint32_t)C * 2u;     // one block's q|k|v image
         for (size_t i = 0; i < h->down.size(); ++i) {
@@ -369,7 +430,7 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
             if (blk.kind == ASTTS_FLOW_RESAMPLE_DOWN) {
                 RUN(k.gemm(cur, 0, blk.resample, nullptr, nxt, 0, (int64_t)b2 * t_half, tt, t_half, 2, 1, ASTTS_ACT_NONE));
                 tt = t_half;
-                L = B.lens_half;
+                L = lens_half;
             } else {
                 RUN(k.gemm(cur, 0, blk.resample, nullptr, nxt, 0, (int64_t)b2 * tt, tt, tt, 1, 1, ASTTS_ACT_NONE));
             }
@@ -428,16 +489,273 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
         }
         // final block at the full resolution (tt == t here: the last up block restores it)
         float* fin = const_cast<float*>(up_src);
-        RUN(k.mask(fin, B.lens_full, t, C));
+        RUN(k.mask(fin, lens_full, t, C));
         RUN(k.gemm(fin, 0, c.fin_c, nullptr, B.r1, 0, (int64_t)b2 * t, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(astts_op_groupnorm(B.r1, B.lens_full, c.fin_g_w, c.fin_g_b, nullptr, B.r3, 0, b2, t, C, c.groups, 1e-5f, 1, B.gn_ws,
-                               B.gn_ws_bytes, st));
+        RUN(k.gnorm(B.r1, lens_full, c.fin_g_w, c.fin_g_b, nullptr, B.r3, 0, t));
         RUN(k.gemm(B.r3, 0, c.fin_p, nullptr, B.d, 0, (int64_t)b2 * t, t, t, 1, 0, ASTTS_ACT_NONE));
-        RUN(k.mask(B.d, B.lens_full, t, mel));
-        // x += dt * ((1 + r) d_cond - r d_uncond)
-        RUN(astts_op_elementwise(ASTTS_EL_CFG_EULER, x, B.d, nullptr, nullptr, x, (int64_t)b * t * mel, t, mel, dt_host[s], cfg_rate, st));
+        RUN(k.mask(B.d, lens_full, t, mel));
+        // x += dt * ((1 + r) d_cond - r d_uncond), every batch with its own dt and rate on its own sequences of d
+        for (int i = 0; i < k.n_seg; ++i) {
+            const Seg& g = k.seg[i];
+            RUN(astts_op_elementwise(ASTTS_EL_CFG_EULER, g.x, B.d + (size_t)g.seq0 * t * mel, nullptr, nullptr, g.x, (int64_t)g.b * t * mel, t, mel,
+                                     g.dt, g.cfg_rate, k.st));
+        }
       }
+    return ASTTS_OK;
+}
+
+}  // namespace
+
+// What a joined pass reads of every batch it carries, passed by value: the batch's sequence range, where its time projections of all
+// its steps and its lengths live, and the Euler step it is at.
+struct FlowJoinTable {
+    const float* tproj[astts::FlowSessionPlan::kSlots];
+    const int* lens_full[astts::FlowSessionPlan::kSlots];
+    const int* lens_half[astts::FlowSessionPlan::kSlots];
+    int seq0[astts::FlowSessionPlan::kSlots], b2[astts::FlowSessionPlan::kSlots], trows[astts::FlowSessionPlan::kSlots],
+        step[astts::FlowSessionPlan::kSlots];
+    int n;
+};
+
+// tproj_out [n_res][nseq][C]: every sequence's time projection rows of its batch's CURRENT step, gathered into the contiguous block per
+// ResNet block that the kernels read; lens_full / lens_half [nseq]: the batches' lengths side by side
+__global__ __launch_bounds__(256) void flow_join_assemble(FlowJoinTable T, float* __restrict__ tproj_out, int* __restrict__ lens_full,
+                                                         int* __restrict__ lens_half, int nseq, int n_res, int C) {
+    const int64_t total = (int64_t)n_res * nseq * C;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int cc = (int)(i % C);
+        const int seq = (int)((i / C) % nseq);
+        const int ri = (int)(i / ((int64_t)C * nseq));
+        int k = 0;
+        while (k + 1 < T.n && seq >= T.seq0[k] + T.b2[k]) ++k;
+        const int j = seq - T.seq0[k];
+        tproj_out[i] = T.tproj[k][((int64_t)ri * T.trows[k] + (int64_t)T.step[k] * T.b2[k] + j) * C + cc];
+        if (i < nseq) {       // (i < nseq <= C * nseq: here seq == 0, so the sequence of element i is looked up again)
+            int kk = 0;
+            while (kk + 1 < T.n && (int)i >= T.seq0[kk] + T.b2[kk]) ++kk;
+            lens_full[i] = T.lens_full[kk][(int)i - T.seq0[kk]];
+            lens_half[i] = T.lens_half[kk][(int)i - T.seq0[kk]];
+        }
     }
+}
+
+struct astts_flow_session {
+    astts_flow* h;
+    astts::FlowSessionPlan plan;
+    astts_stream_t st;
+    Buffers B;                      // of a pass over 2 * rows_max sequences
+    struct Slot {
+        Seg seg;
+        TimeBufs T;                 // the batch's time path, all its steps
+        int *lens_full, *lens_half; // [2 b]
+        bool full;
+        float dt[FLOW_MAX_STEPS];
+    } slot[astts::FlowSessionPlan::kSlots];
+    int passes, carried;            // passes enqueued; batches they carried (summed)
+};
+
+namespace {
+
+// one carve-up serves astts_flow_session_bytes (base == nullptr) and astts_flow_session_create: the buffers of a pass over the
+// session's maximum (carve), then every slot's time path and lengths
+size_t carve_session(const astts_flow* h, int t, int n_slots, int rows_max, int steps_max, char* base, astts_flow_session* S) {
+    const astts_flow_config_t& c = h->cfg;
+    size_t o = carve(h, rows_max, t, base, S ? &S->B : nullptr);
+    auto take = [&](size_t bytes) {
+        void* p = base ? base + o : nullptr;
+        o = align_up(o + bytes, 256);
+        return p;
+    };
+    const size_t n_res = h->down.size() + h->mid.size() + h->up.size();
+    const size_t trows = (size_t)steps_max * 2 * rows_max;
+    for (int i = 0; i < n_slots; ++i) {
+        astts_flow_session::Slot tmp;
+        astts_flow_session::Slot& X = S ? S->slot[i] : tmp;
+        X.T.tv = (float*)take(sizeof(float) * trows);
+        X.T.temb0 = (float*)take(sizeof(float) * trows * c.time_in);
+        X.T.temb1 = (float*)take(sizeof(float) * trows * c.time_dim);
+        X.T.temb2 = (float*)take(sizeof(float) * trows * c.time_dim);
+        X.T.tproj = (float*)take(sizeof(float) * n_res * trows * c.channels);
+        X.lens_full = (int*)take(sizeof(int) * 2 * rows_max);
+        X.lens_half = (int*)take(sizeof(int) * 2 * rows_max);
+    }
+    return o;
+}
+
+}  // namespace
+
+extern "C" {
+
+int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* spk, const float* cond, const int32_t* lens,
+                     int32_t b, int32_t t, int32_t n_steps, const float* t_host, const float* dt_host, float cfg_rate,
+                     void* workspace, size_t workspace_bytes, astts_stream_t stream) {
+    ASTTS_REQUIRE(h && x && mu && spk && cond && t_host && dt_host && workspace, ASTTS_ERR_INVALID, "astts_flow_solve: null argument");
+    ASTTS_REQUIRE(b >= 1 && t >= 2 && n_steps >= 1, ASTTS_ERR_INVALID, "astts_flow_solve: b=%d t=%d n_steps=%d", b, t, n_steps);
+    ASTTS_REQUIRE(workspace_bytes >= astts_flow_workspace_bytes(h, b, t) && ((uintptr_t)workspace & 255) == 0,
+                  ASTTS_ERR_WORKSPACE, "astts_flow_solve: workspace too small or misaligned");
+    hipStream_t st = (hipStream_t)stream;
+    Seg seg{x, mu, spk, cond, 0, b, 0.0f, cfg_rate};
+    Ctx k;
+    k.h = h;
+    k.b2 = 2 * b;
+    k.T = t;
+    k.full = lens == nullptr;
+    k.st = stream;
+    k.seg = &seg;
+    k.n_seg = 1;
+    carve(h, b, t, (char*)workspace, &k.B);
+    const Buffers& B = k.B;
+    const int b2 = k.b2, C = h->cfg.channels;
+
+    hipLaunchKernelGGL(flow_fill_lens, dim3((b2 + 63) / 64), dim3(64), 0, st, lens, B.lens_full, B.lens_half, b, t);
+    ASTTS_CHECK_LAUNCH();
+
+    // the time path of all steps before the first one (time_path); solves with more than FLOW_MAX_STEPS steps evaluate it chunk by
+    // chunk (the workspace holds FLOW_MAX_STEPS steps)
+    const TimeBufs T{B.tv, B.temb0, B.temb1, B.temb2, B.tproj};
+    for (int s = 0; s < n_steps; ++s) {
+        const int s0 = s - s % FLOW_MAX_STEPS, sl = s - s0;
+        const int steps = n_steps - s0 < FLOW_MAX_STEPS ? n_steps - s0 : FLOW_MAX_STEPS;
+        if (sl == 0) RUN(time_path(k, T, t_host + s0, steps, b2));
+        seg.dt = dt_host[s];
+        RUN(estimator_pass(k, B.tproj + (size_t)sl * b2 * C, (size_t)steps * b2 * C, B.lens_full, B.lens_half));
+    }
+    return ASTTS_OK;
+}
+
+size_t astts_flow_session_bytes(const astts_flow_t* h, int32_t t, int32_t n_slots, int32_t rows_max, int32_t steps_max) {
+    astts::FlowSessionPlan p;
+    if (!h || p.init(t, n_slots, rows_max, steps_max) != astts::FLOW_SESSION_OK || steps_max > FLOW_MAX_STEPS) return 0;
+    return carve_session(h, t, n_slots, rows_max, steps_max, nullptr, nullptr);
+}
+
+int astts_flow_session_create(astts_flow_t* h, int32_t t, int32_t n_slots, int32_t rows_max, int32_t steps_max, void* workspace,
+                              size_t workspace_bytes, astts_stream_t stream, astts_flow_session_t** out) {
+    ASTTS_REQUIRE(h && workspace && out, ASTTS_ERR_INVALID, "astts_flow_session_create: null argument");
+    astts::FlowSessionPlan p;
+    ASTTS_REQUIRE(p.init(t, n_slots, rows_max, steps_max) == astts::FLOW_SESSION_OK && steps_max <= FLOW_MAX_STEPS, ASTTS_ERR_INVALID,
+                  "astts_flow_session_create: t=%d n_slots=%d rows_max=%d steps_max=%d", t, n_slots, rows_max, steps_max);
+    ASTTS_REQUIRE(workspace_bytes >= astts_flow_session_bytes(h, t, n_slots, rows_max, steps_max) && ((uintptr_t)workspace & 255) == 0,
+                  ASTTS_ERR_WORKSPACE, "astts_flow_session_create: workspace too small or misaligned");
+    astts_flow_session* s = new astts_flow_session();
+    s->h = h;
+    s->plan = p;
+    s->st = stream;
+    s->passes = s->carried = 0;
+    carve_session(h, t, n_slots, rows_max, steps_max, (char*)workspace, s);
+    *out = s;
+    return ASTTS_OK;
+}
+
+int astts_flow_session_destroy(astts_flow_session_t* s) {
+    delete s;
+    return ASTTS_OK;
+}
+
+int astts_flow_session_can_admit(const astts_flow_session_t* s, int32_t b, int32_t t, int32_t n_steps) {
+    return s ? s->plan.admissible(b, t, n_steps) : astts::FLOW_SESSION_ERR_ARG;
+}
+
+int astts_flow_session_admit(astts_flow_session_t* s, float* x, const float* mu, const float* spk, const float* cond, const int32_t* lens,
+                             int32_t b, int32_t t, int32_t n_steps, const float* t_host, const float* dt_host, float cfg_rate,
+                             int32_t* slot_out) {
+    ASTTS_REQUIRE(s && x && mu && spk && cond && t_host && dt_host && slot_out, ASTTS_ERR_INVALID, "astts_flow_session_admit: null argument");
+    const int slot = s->plan.admissible(b, t, n_steps);
+    ASTTS_REQUIRE(slot >= 0, ASTTS_ERR_INVALID, "astts_flow_session_admit: b=%d t=%d n_steps=%d is not admissible now (%d)", b, t, n_steps, slot);
+    astts_flow_session::Slot& X = s->slot[slot];
+    X.seg = Seg{x, mu, spk, cond, 0, b, 0.0f, cfg_rate};
+    X.full = lens == nullptr;
+    for (int i = 0; i < n_steps; ++i) X.dt[i] = dt_host[i];
+    hipLaunchKernelGGL(flow_fill_lens, dim3((2 * b + 63) / 64), dim3(64), 0, (hipStream_t)s->st, lens, X.lens_full, X.lens_half, b, t);
+    ASTTS_CHECK_LAUNCH();
+    Ctx k;
+    k.h = s->h;
+    k.B = s->B;
+    k.b2 = 2 * b;
+    k.T = t;
+    k.full = X.full;
+    k.st = s->st;
+    k.seg = &X.seg;
+    k.n_seg = 1;
+    RUN(time_path(k, X.T, t_host, n_steps, 2 * b));
+    s->plan.admit(b, t, n_steps);
+    *slot_out = slot;
+    return ASTTS_OK;
+}
+
+int astts_flow_session_step(astts_flow_session_t* s, int32_t n_passes, uint32_t* finished_mask_out) {
+    ASTTS_REQUIRE(s && finished_mask_out && n_passes >= 1, ASTTS_ERR_INVALID, "astts_flow_session_step: bad argument");
+    using astts::FlowSessionPlan;
+    const int C = s->h->cfg.channels;
+    const int n_res = (int)(s->h->down.size() + s->h->mid.size() + s->h->up.size());
+    uint32_t done = 0;
+    *finished_mask_out = 0;
+    for (int p = 0; p < n_passes && s->plan.n_active() > 0; ++p) {
+        const int nseq = s->plan.layout();
+        Seg segs[FlowSessionPlan::kSlots];
+        int of[FlowSessionPlan::kSlots];
+        int n = 0;
+        bool full = true;
+        for (int i = 0; i < s->plan.n_slots; ++i) {
+            const astts::FlowSlot& ps = s->plan.s[i];
+            if (!ps.active) continue;
+            segs[n] = s->slot[i].seg;
+            segs[n].seq0 = ps.seq0;
+            segs[n].dt = s->slot[i].dt[ps.step];
+            full = full && s->slot[i].full;
+            of[n++] = i;
+        }
+        Ctx k;
+        k.h = s->h;
+        k.B = s->B;
+        k.b2 = nseq;
+        k.T = s->plan.t;
+        k.full = full;
+        k.st = s->st;
+        k.seg = segs;
+        k.n_seg = n;
+        if (n == 1) {       // a lone batch: the launches of astts_flow_solve, on the batch's own tables
+            const astts_flow_session::Slot& X = s->slot[of[0]];
+            const astts::FlowSlot& ps = s->plan.s[of[0]];
+            RUN(estimator_pass(k, X.T.tproj + (size_t)ps.step * nseq * C, (size_t)ps.n_steps * nseq * C, X.lens_full, X.lens_half));
+        } else {
+            FlowJoinTable T{};
+            T.n = n;
+            for (int j = 0; j < n; ++j) {
+                const astts::FlowSlot& ps = s->plan.s[of[j]];
+                T.tproj[j] = s->slot[of[j]].T.tproj;
+                T.lens_full[j] = s->slot[of[j]].lens_full;
+                T.lens_half[j] = s->slot[of[j]].lens_half;
+                T.seq0[j] = ps.seq0;
+                T.b2[j] = 2 * ps.b;
+                T.trows[j] = ps.n_steps * 2 * ps.b;
+                T.step[j] = ps.step;
+            }
+            hipLaunchKernelGGL(flow_join_assemble, dim3(grid_for((int64_t)n_res * nseq * C)), dim3(256), 0, (hipStream_t)s->st, T, s->B.tproj,
+                               s->B.lens_full, s->B.lens_half, nseq, n_res, C);
+            ASTTS_CHECK_LAUNCH();
+            RUN(estimator_pass(k, s->B.tproj, (size_t)nseq * C, s->B.lens_full, s->B.lens_half));
+        }
+        s->passes += 1;
+        s->carried += n;
+        done |= s->plan.advance();
+    }
+    *finished_mask_out = done;
+    return ASTTS_OK;
+}
+
+int astts_flow_session_state(const astts_flow_session_t* s, int32_t* out8) {
+    ASTTS_REQUIRE(s && out8, ASTTS_ERR_INVALID, "astts_flow_session_state: null argument");
+    int mask = 0;
+    for (int i = 0; i < astts::FlowSessionPlan::kSlots; ++i) {
+        const astts::FlowSlot& ps = s->plan.s[i];
+        mask |= ps.active << i;
+        out8[4 + i] = ps.active ? ps.n_steps - ps.step : 0;
+    }
+    out8[0] = mask;
+    out8[1] = s->plan.rows_active();
+    out8[2] = s->passes;
+    out8[3] = s->carried;
     return ASTTS_OK;
 }
 
