@@ -148,10 +148,12 @@ def gemm(x: torch.Tensor, w: PackedWeight, act: str = "none", residual: Optional
          row_scale: Optional[torch.Tensor] = None, alpha: float = 1.0, slope: float = 0.1,
          t_in: Optional[int] = None, t_out: Optional[int] = None, stride: int = 1, dil: int = 1, pad: int = 0,
          out: Optional[torch.Tensor] = None, use_bias: bool = True, out_dtype=torch.float32,
-         in_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+         in_lens: Optional[torch.Tensor] = None, plan_m: Optional[int] = None) -> torch.Tensor:
     """``x``: ``[..., cin]`` fp32 or fp16 (rows = batch*time); conv geometry via t_in/t_out/stride/dil/pad.
     ``out_dtype=torch.float16`` when the result only feeds MFMA consumers (another GEMM / attention).
-    ``in_lens`` (int32 ``[batches]``, ragged batches): input steps at or beyond a row's length read as zero."""
+    ``in_lens`` (int32 ``[batches]``, ragged batches): input steps at or beyond a row's length read as zero.
+    ``plan_m``: run the kernel the launcher plans for ``plan_m`` rows over all rows (astts_op_gemm_planned: several batches of
+    ``plan_m`` rows in the launch each gets alone)."""
     x = _act_in(x)
     cin = x.shape[-1]
     assert cin == w.cin, (cin, w.cin)
@@ -172,10 +174,15 @@ def gemm(x: torch.Tensor, w: PackedWeight, act: str = "none", residual: Optional
         ldr = residual.shape[-1]
     if in_lens is not None:
         assert in_lens.dtype == torch.int32 and in_lens.numel() == batches and in_lens.is_cuda
-    _lib.check(_L().astts_op_gemm(x.data_ptr(), 1 if x.dtype == torch.float16 else 0, w.data.data_ptr(),
-                                  _p(w.bias) if use_bias else None, _p(residual), _p(row_scale), out.data_ptr(),
-                                  1 if out.dtype == torch.float16 else 0, m, w.n, w.cin, w.cin_pad, w.taps, cin, ldc, ldr,
-                                  t_in, t_out, stride, dil, pad, ACT[act], alpha, slope, _p(in_lens), _st()))
+    args = (x.data_ptr(), 1 if x.dtype == torch.float16 else 0, w.data.data_ptr(),
+            _p(w.bias) if use_bias else None, _p(residual), _p(row_scale), out.data_ptr(),
+            1 if out.dtype == torch.float16 else 0, m, w.n, w.cin, w.cin_pad, w.taps, cin, ldc, ldr,
+            t_in, t_out, stride, dil, pad, ACT[act], alpha, slope, _p(in_lens))
+    if plan_m is None:
+        _lib.check(_L().astts_op_gemm(*args, _st()))
+    else:
+        from . import _lib_session
+        _lib.check(_lib_session.load().astts_op_gemm_planned(*args, int(plan_m), _st()))
     return out
 
 
@@ -480,20 +487,35 @@ def tfm_ffn_fused_supported(c: int, hidden: int) -> bool:
 
 
 def tfm_ffn_fused(x: torch.Tensor, w1: PackedWeight, w1_frag: torch.Tensor, w2: PackedWeight, w2_frag: torch.Tensor, eps: float = 1e-5,
-                  attn: Optional[torch.Tensor] = None, wo: Optional[PackedWeight] = None, wo_frag: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  attn: Optional[torch.Tensor] = None, wo: Optional[PackedWeight] = None, wo_frag: Optional[torch.Tensor] = None,
+                  segments=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``x' + W2 gelu(W1 LayerNorm(x') + b1) + b2`` in one launch (LayerNorm affine folded into ``w1``): x fp32 ``[..., 256]``.
     With ``attn`` (fp16 ``[..., k0]``), ``wo`` and ``wo_frag = tfm_pack_frag(wo)``: ``x' = x + attn Wo^T + bo`` (the attention's
-    output projection and residual, in the same launch); otherwise ``x' = x``."""
+    output projection and residual, in the same launch); otherwise ``x' = x``.
+    ``segments``: ``[(row0, rows), ...]`` -- one launch over these row ranges, each cut into tiles of its own
+    (astts_op_tfm_ffn_fused_seg); rows outside every segment are not written.  ``out``: the result tensor (``x`` itself: in place)."""
     x = _f32(x)
     c, hidden = x.shape[-1], w1.n
     assert w1.cin == c and w2.cin == hidden and w2.n == c and w1_frag.shape == (hidden, c) and w2_frag.shape == (c, hidden)
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape
     m = x.numel() // c
     k0 = 0
     if attn is not None:
         k0 = attn.shape[-1]
         assert attn.dtype == torch.float16 and attn.is_contiguous() and attn.numel() // k0 == m
         assert wo is not None and wo.n == c and wo.cin == k0 and wo_frag.shape == (c, k0)
+    if segments is not None:
+        from . import _lib_session
+        n = len(segments)
+        assert all(0 <= r0 and r0 + r <= m for r0, r in segments), (segments, m)      # the kernel trusts the table
+        row0 = (c_int64 * n)(*[int(r0) for r0, _ in segments])
+        rows = (c_int64 * n)(*[int(r) for _, r in segments])
+        _lib.check(_lib_session.load().astts_op_tfm_ffn_fused_seg(
+            x.data_ptr(), w1_frag.data_ptr(), _p(w1.bias), w2_frag.data_ptr(), _p(w2.bias), out.data_ptr(), n, ctypes.addressof(row0),
+            ctypes.addressof(rows), c, hidden, eps, _p(attn), _p(wo_frag), _p(wo.bias) if wo is not None else None, k0, None, 0, _st()))
+        return out
     _lib.check(_L().astts_op_tfm_ffn_fused(x.data_ptr(), w1_frag.data_ptr(), _p(w1.bias), w2_frag.data_ptr(), _p(w2.bias), out.data_ptr(),
                                            m, c, hidden, eps, _p(attn), _p(wo_frag), _p(wo.bias) if wo is not None else None, k0, None, 0,
                                            _st()))

@@ -14,8 +14,11 @@
 // outputs) are fp16.
 #include "common.h"
 #include "flow_session.h"
+#include "flow_share.h"
 #include "../../include/session/astts_flow_session.h"
+#include "../../include/session/astts_flow_share.h"
 
+#include <cstdlib>
 #include <vector>
 
 struct astts_flow {
@@ -86,6 +89,10 @@ __global__ void flow_fill_time(float* __restrict__ tv, float value, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) tv[i] = value;
 }
+
+// ops_gemm.hip: what gemm_plan reads of an astts_op_gemm call, m aside
+GemmShape gemm_shape_of_call(const void* x, int x_f16, int out_f16, int n, int cin, int cin_pad, int taps, int lda, int t_in, int t_out,
+                             int stride, int pad);
 
 static inline int grid_for(int64_t total) {
     int64_t g = (total + 255) / 256;
@@ -170,38 +177,54 @@ struct Ctx {
     int b2, T;          // b2: sequences of the pass (all batches')
     bool full;
     astts_stream_t st;
-    const Seg* seg;     // the batches of the pass; astts_flow_solve: one
+    const Seg* seg;     // the batches of the pass, one after the other without gaps; astts_flow_solve: one
     int n_seg;
+    bool share;         // a joined pass issues ONE feed-forward launch and one GEMM launch per group of equal plans (flow_share.h)
 
     int gemm1(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
               int t_in, int t_out, int stride, int pad, int act) const {
         return astts_op_gemm(x, x16, w.w, w.bias, residual, nullptr, out, out16, m, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
                              residual ? w.n : 0, t_in, t_out, stride, 1, pad, act, 1.0f, 0.1f, nullptr, st);
     }
-    // a convolution over all sequences ([b2, t_in, cin] -> [b2, t_out, n]).  launch_gemm plans kernel and tile from the TOTAL row count
-    // (gemm_plan.h), so a joined pass issues it once per batch over the batch's own rows: the launch that batch gets alone.
+    // a convolution over all sequences ([b2, t_in, cin] -> [b2, t_out, n]).  launch_gemm plans kernel family and tile from the row count
+    // (gemm_plan.h), and a row's sum depends on the kernel, not on where its tile lies.  A joined pass therefore groups consecutive
+    // batches whose plans FOR THEIR OWN ROW COUNTS are equal (gemm_share_groups) and issues one launch per group with that plan
+    // (astts_op_gemm_planned): the kernel each of them gets alone, over the rows of all.  Batches whose plans differ, and the m <= 32
+    // family, stay separate.  So does every GEMM with an activation: the epilogue of a tile that lies wholly inside the output evaluates
+    // GELU with gelu_erf_fast, the epilogue of an edge tile with erff (gemm_kernels.h), so a batch's last rows would change their bits when
+    // another batch's rows complete their tile (the unfused feed-forward's W1; found by the tiny-width session tests).
+    // `per_seq`: false = a projection of rows (t_in == t_out == the launch's row count, as linear()).
     int gemm(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
-             int t_in, int t_out, int stride, int pad, int act) const {
-        if (n_seg == 1) return gemm1(x, x16, w, residual, out, out16, m, t_in, t_out, stride, pad, act);
-        for (int i = 0; i < n_seg; ++i) {
-            const int64_t s0 = seg[i].seq0, nb = 2 * (int64_t)seg[i].b;
-            RUN(gemm1((const char*)x + s0 * t_in * w.cin * (x16 ? 2 : 4), x16, w, residual ? residual + s0 * t_out * w.n : nullptr,
-                      (char*)out + s0 * t_out * w.n * (out16 ? 2 : 4), out16, nb * t_out, t_in, t_out, stride, pad, act));
+             int t_in, int t_out, int stride, int pad, int act, bool per_seq = true) const {
+        if (n_seg == 1) return gemm1(x, x16, w, residual, out, out16, m, per_seq ? t_in : (int)m, per_seq ? t_out : (int)m, stride, pad, act);
+        int64_t rows[FlowSessionPlan::kSlots];
+        for (int i = 0; i < n_seg; ++i) rows[i] = 2 * (int64_t)seg[i].b * t_out;
+        const GemmGroups G = gemm_share_groups(gemm_shape_of_call(x, x16, out16, w.n, w.cin, w.cin_pad, w.taps, w.cin, t_in, t_out, stride, pad),
+                                               n_seg, rows, share && act == ASTTS_ACT_NONE);
+        for (int g = 0; g < G.n; ++g) {
+            const int64_t s0 = seg[G.first[g]].seq0;
+            int64_t gm = 0;
+            for (int i = 0; i < G.count[g]; ++i) gm += rows[G.first[g] + i];
+            const int ti = per_seq ? t_in : (int)gm, to = per_seq ? t_out : (int)gm;
+            RUN(astts_op_gemm_planned((const char*)x + s0 * t_in * w.cin * (x16 ? 2 : 4), x16, w.w, w.bias, residual ? residual + s0 * t_out * w.n : nullptr,
+                                      nullptr, (char*)out + s0 * t_out * w.n * (out16 ? 2 : 4), out16, gm, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
+                                      residual ? w.n : 0, ti, to, stride, 1, pad, act, 1.0f, 0.1f, nullptr, G.plan_m[g], st));
         }
         return ASTTS_OK;
     }
     int linear(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m, int act) const {
         return gemm1(x, x16, w, residual, out, out16, m, (int)m, (int)m, 1, 0, act);
     }
-    // a projection of the rows of all sequences ([b2 * t, cin] -> [b2 * t, n]): per batch in a joined pass, as gemm()
+    // a projection of the rows of all sequences ([b2 * t, cin] -> [b2 * t, n]): grouped by plan in a joined pass, as gemm()
     int linear_seq(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int t, int act) const {
-        if (n_seg == 1) return linear(x, x16, w, residual, out, out16, (int64_t)b2 * t, act);
+        return gemm(x, x16, w, residual, out, out16, (int64_t)b2 * t, t, t, 1, 0, act, false);
+    }
+    // the rows of every batch of the pass at t frames per sequence, for the segmented feed-forward launch
+    void seg_rows(int t, int64_t* row0, int64_t* rows) const {
         for (int i = 0; i < n_seg; ++i) {
-            const int64_t r0 = (int64_t)seg[i].seq0 * t, m = 2 * (int64_t)seg[i].b * t;
-            RUN(linear((const char*)x + r0 * w.cin * (x16 ? 2 : 4), x16, w, residual ? residual + r0 * w.n : nullptr,
-                       (char*)out + r0 * w.n * (out16 ? 2 : 4), out16, m, act));
+            row0[i] = (int64_t)seg[i].seq0 * t;
+            rows[i] = 2 * (int64_t)seg[i].b * t;
         }
-        return ASTTS_OK;
     }
     // GroupNorm (+ time projection, Mish) of all sequences: astts_op_groupnorm sizes its grid by the sequence count, so per batch too
     int gnorm(const float* x, const int* lens, const float* gw, const float* gb, const float* add_bc, void* y, int y16, int t) const {
@@ -270,24 +293,32 @@ struct Ctx {
         const bool ffn = w.w1_frag && w.w2_frag && astts_op_tfm_ffn_fused_supported(C, w.w1.n);
         // output projection + residual + LayerNorm + W1 + GELU + W2 + residual in one launch (in place on p); faster than the
         // separate projection at every row count measured (5 504: 20.2 vs 26.8 us, 11 008: 36.6 vs 45.0, 44 032: 116 vs 128)
-        // tfm_ffn_fused sums the hidden chunks in an order rotated by the workgroup's index (a 32-row tile starts at chunk
-        // (tile / 8) % chunks): a row's bits depend on where its tile lies in the launch.  A joined pass therefore issues it per batch,
-        // over the batch's own rows from tile 0 -- the launch that batch gets alone.
-        if (ffn && w.wo_frag && (hd == 256 || hd == 512)) {
+        // tfm_ffn_fused sums the hidden chunks in an order rotated by the tile's index (a 32-row tile starts at chunk (tile / 8) % chunks):
+        // a row's bits depend on where its tile lies.  A joined pass issues ONE launch over a segment table (astts_op_tfm_ffn_fused_seg):
+        // every batch's rows are cut into tiles of their own, counted from the batch's first tile, so each row runs what it runs when
+        // its batch is launched alone; the launch prefetches next_w.  ASTTS_FLOW_SHARE=0 (share == false) restores one launch per batch.
+        // What stays per batch in a joined pass: astts_op_groupnorm (its grid form depends on the sequence count; three launches per
+        // pass), flow_pack_input and the CFG-Euler update (each batch's own tensors), and GEMMs whose plans differ (gemm()).
+        const bool ffn_wo = ffn && w.wo_frag && (hd == 256 || hd == 512);
+        if (!ffn_wo) RUN(linear_seq(B.a16, 1, w.wo, p, q, 0, t, ASTTS_ACT_NONE));
+        if (ffn) {    // (output projection + residual +) LayerNorm + W1 + GELU + W2 + residual: one launch, in place on p with the projection
+            const float* in = ffn_wo ? p : q;
+            const _Float16* attn = ffn_wo ? B.a16 : nullptr;
+            const void* wo = ffn_wo ? w.wo_frag : nullptr;
+            const float* bo = ffn_wo ? w.wo.bias : nullptr;
+            const int k0 = ffn_wo ? hd : 0;
+            if (n_seg == 1)
+                return astts_op_tfm_ffn_fused(in, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, attn, wo, bo, k0,
+                                              ffn_wo ? next_w : nullptr, ffn_wo ? next_bytes : 0u, st);
+            int64_t row0[FlowSessionPlan::kSlots], nrows[FlowSessionPlan::kSlots];
+            seg_rows(t, row0, nrows);
+            if (share)
+                return astts_op_tfm_ffn_fused_seg(in, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, n_seg, row0, nrows, C, w.w1.n, 1e-5f, attn, wo,
+                                                  bo, k0, ffn_wo ? next_w : nullptr, ffn_wo ? next_bytes : 0u, st);
             for (int i = 0; i < n_seg; ++i) {
-                const int64_t r0 = n_seg == 1 ? 0 : (int64_t)seg[i].seq0 * t, m = n_seg == 1 ? rows : 2 * (int64_t)seg[i].b * t;
-                const bool last = i + 1 == n_seg;
-                RUN(astts_op_tfm_ffn_fused(p + r0 * C, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p + r0 * C, m, C, w.w1.n, 1e-5f, B.a16 + r0 * hd,
-                                           w.wo_frag, w.wo.bias, hd, last ? next_w : nullptr, last ? next_bytes : 0u, st));
-            }
-            return ASTTS_OK;
-        }
-        RUN(linear_seq(B.a16, 1, w.wo, p, q, 0, t, ASTTS_ACT_NONE));
-        if (ffn) {    // LayerNorm + W1 + GELU + W2 + residual: one launch
-            for (int i = 0; i < n_seg; ++i) {
-                const int64_t r0 = n_seg == 1 ? 0 : (int64_t)seg[i].seq0 * t, m = n_seg == 1 ? rows : 2 * (int64_t)seg[i].b * t;
-                RUN(astts_op_tfm_ffn_fused(q + r0 * C, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p + r0 * C, m, C, w.w1.n, 1e-5f, nullptr, nullptr,
-                                           nullptr, 0, nullptr, 0, st));
+                const bool last = ffn_wo && i + 1 == n_seg;
+                RUN(astts_op_tfm_ffn_fused(in + row0[i] * C, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p + row0[i] * C, nrows[i], C, w.w1.n, 1e-5f,
+                                           attn ? attn + row0[i] * hd : nullptr, wo, bo, k0, last ? next_w : nullptr, last ? next_bytes : 0u, st));
             }
             return ASTTS_OK;
         }
@@ -603,6 +634,7 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
     k.st = stream;
     k.seg = &seg;
     k.n_seg = 1;
+    k.share = false;
     carve(h, b, t, (char*)workspace, &k.B);
     const Buffers& B = k.B;
     const int b2 = k.b2, C = h->cfg.channels;
@@ -677,6 +709,7 @@ int astts_flow_session_admit(astts_flow_session_t* s, float* x, const float* mu,
     k.st = s->st;
     k.seg = &X.seg;
     k.n_seg = 1;
+    k.share = false;
     RUN(time_path(k, X.T, t_host, n_steps, 2 * b));
     s->plan.admit(b, t, n_steps);
     *slot_out = slot;
@@ -690,6 +723,10 @@ int astts_flow_session_step(astts_flow_session_t* s, int32_t n_passes, uint32_t*
     const int n_res = (int)(s->h->down.size() + s->h->mid.size() + s->h->up.size());
     uint32_t done = 0;
     *finished_mask_out = 0;
+    // ASTTS_FLOW_SHARE=0: every batch of a joined pass gets its own feed-forward and GEMM launches (tests, A/B).  Read per call: the tests
+    // switch inside one process.
+    const char* se = getenv("ASTTS_FLOW_SHARE");
+    const bool share = !(se && atoi(se) == 0);
     for (int p = 0; p < n_passes && s->plan.n_active() > 0; ++p) {
         const int nseq = s->plan.layout();
         Seg segs[FlowSessionPlan::kSlots];
@@ -714,6 +751,7 @@ int astts_flow_session_step(astts_flow_session_t* s, int32_t n_passes, uint32_t*
         k.st = s->st;
         k.seg = segs;
         k.n_seg = n;
+        k.share = share;
         if (n == 1) {       // a lone batch: the launches of astts_flow_solve, on the batch's own tables
             const astts_flow_session::Slot& X = s->slot[of[0]];
             const astts::FlowSlot& ps = s->plan.s[of[0]];

@@ -20,6 +20,8 @@
 //                   template arguments or the plan, and sets the dynamic-LDS attribute once under a std::once_flag.
 #include "gemm_kernels.h"
 #include "gemm_plan.h"
+#include "flow_share.h"
+#include "../../include/session/astts_flow_share.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -190,10 +192,35 @@ static GemmShape gemm_shape(const GemmArgs& a) {
     return s;
 }
 
+// what gemm_plan reads of an astts_op_gemm call, m aside (flow_engine.hip groups the batches of a joined pass by their plans)
+GemmShape gemm_shape_of_call(const void* x, int x_f16, int out_f16, int n, int cin, int cin_pad, int taps, int lda, int t_in, int t_out,
+                             int stride, int pad) {
+    GemmArgs a;
+    a.x = (const float*)x;
+    a.n = n;
+    a.cin = cin;
+    a.cin_pad = cin_pad;
+    a.taps = taps;
+    a.lda = lda;
+    a.t_in = t_in;
+    a.t_out = t_out;
+    a.stride = stride;
+    a.pad = pad;
+    a.x_f16 = x_f16 ? 1 : 0;
+    a.out_f16 = out_f16 ? 1 : 0;
+    return gemm_shape(a);
+}
+
 // Every GEMM call: shape -> plan -> the launcher of the planned kernel.  What runs is decided in gemm_plan.h and nowhere else.
-static int launch_gemm(const GemmArgs& a, hipStream_t st) {
-    const GemmPlan p = gemm_plan(gemm_shape(a));
+// plan_m > 0: the plan is the one gemm_plan() gives plan_m rows, the kernel runs over all a.m rows (grid, bounds and the skinny
+// kernel's passes follow a.m): the rows of several batches in the launch each batch gets alone (flow_share.h).
+static int launch_gemm(const GemmArgs& a, hipStream_t st, int64_t plan_m = 0) {
+    GemmShape shape = gemm_shape(a);
+    if (plan_m > 0) shape.m = plan_m;
+    const GemmPlan p = gemm_plan(shape);
     const bool skinny = p.kind == ASTTS_GEMM_KIND_SKINNY;
+    ASTTS_REQUIRE(gemm_plan_serves(p, a.m), ASTTS_ERR_UNSUPPORTED,
+                  "astts_op_gemm_planned: the plan of %lld rows is the m <= 32 family, which does not serve m=%lld", (long long)plan_m, (long long)a.m);
     ASTTS_REQUIRE(!skinny || p.fits, ASTTS_ERR_INVALID, "astts_op_gemm: cin_pad=%d does not fit the skinny kernel's LDS image", a.cin_pad);
     ASTTS_REQUIRE(skinny || (!a.gather && !a.ln_gamma && !a.out2), ASTTS_ERR_INVALID,
                   "astts_op_gemm_fused: gather / LayerNorm / split output need m <= 32 and a plain (non-conv) GEMM");
@@ -346,12 +373,12 @@ int astts_op_pack_weight(const float* src, void* dst_f16, int32_t n, int32_t tap
     return ASTTS_OK;
 }
 
-int astts_op_gemm(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
-                  const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
-                  int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
-                  int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
-                  astts_stream_t stream) {
-    const int rc = check_gemm_args("astts_op_gemm", (const float*)x, w_f16, (float*)out, m, n, cin, cin_pad, taps, t_in, t_out, stride, dil, act);
+static int op_gemm(const char* who, const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
+                   const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
+                   int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
+                   int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
+                   int64_t plan_m, astts_stream_t stream) {
+    const int rc = check_gemm_args(who, (const float*)x, w_f16, (float*)out, m, n, cin, cin_pad, taps, t_in, t_out, stride, dil, act);
     if (rc != ASTTS_OK) return rc;
     GemmArgs a = gemm_args(x, w_f16, out, m, n, cin, lda, ldc);
     a.bias = bias;
@@ -371,7 +398,27 @@ int astts_op_gemm(const void* x, int32_t x_f16, const void* w_f16, const float* 
     a.x_f16 = x_f16 ? 1 : 0;
     a.out_f16 = out_f16 ? 1 : 0;
     a.in_lens = in_lens;
-    return launch_gemm(a, (hipStream_t)stream);
+    return launch_gemm(a, (hipStream_t)stream, plan_m);
+}
+
+int astts_op_gemm(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
+                  const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
+                  int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
+                  int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
+                  astts_stream_t stream) {
+    return op_gemm("astts_op_gemm", x, x_f16, w_f16, bias, residual, row_scale, out, out_f16, m, n, cin, cin_pad, taps, lda, ldc, ldr, t_in,
+                   t_out, stride, dil, pad, act, alpha, slope, in_lens, 0, stream);
+}
+
+int astts_op_gemm_planned(const void* x, int32_t x_f16, const void* w_f16, const float* bias, const float* residual,
+                          const float* row_scale, void* out, int32_t out_f16, int64_t m, int32_t n, int32_t cin, int32_t cin_pad,
+                          int32_t taps, int32_t lda, int32_t ldc, int32_t ldr, int32_t t_in, int32_t t_out,
+                          int32_t stride, int32_t dil, int32_t pad, int32_t act, float alpha, float slope, const int32_t* in_lens,
+                          int64_t plan_m, astts_stream_t stream) {
+    ASTTS_REQUIRE(plan_m >= 1 && plan_m <= m, ASTTS_ERR_INVALID, "astts_op_gemm_planned: plan_m=%lld (1 .. m=%lld)", (long long)plan_m,
+                  (long long)m);
+    return op_gemm("astts_op_gemm_planned", x, x_f16, w_f16, bias, residual, row_scale, out, out_f16, m, n, cin, cin_pad, taps, lda, ldc, ldr,
+                   t_in, t_out, stride, dil, pad, act, alpha, slope, in_lens, plan_m, stream);
 }
 
 int astts_op_gemm_rows(const void* x, int32_t x_f16, const void* w_f16,

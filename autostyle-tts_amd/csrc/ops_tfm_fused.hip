@@ -20,7 +20,9 @@
 //            barrier, no global load in the key loop.
 // LDS: K [TKP][72] + V^T [64][TKP + 4] + A [2][32][264] + Q [192][64] halfs = 151 KB at T = 344 (TKP = 352), 159.5 KB at TKP = 384: T <= 384.
 #include "common.h"
+#include "flow_share.h"
 #include "xlane.h"
+#include "../../include/session/astts_flow_share.h"
 
 namespace astts {
 
@@ -500,6 +502,7 @@ struct TfmFfnArgs {
     float eps;
     const char* pf;          // L2 prefetch of the next launch's weights (one range), touched one 128-byte line per thread
     unsigned pf_bytes;
+    FfnSegTable seg;         // m == 0: the launch's row segments (flow_share.h); m > 0: one segment, rows [0, m), and this is not read
 };
 
 // WO: the attention's output projection + residual (the launch between tfm_attn_fused and this one: 8.5 us + boundary) runs as a
@@ -754,8 +757,26 @@ __global__ __launch_bounds__(512, 1) void tfm_ffn_fused(const float* p_x, const 
                                                         int p_hidden, int p_k0, float p_eps, TfmFfnArgs a_in) {
     TfmFfnArgs a = a_in;      // leading parameters: preloaded into SGPRs (see tfm_attn_fused)
     a.x = p_x; a.w1 = p_w1; a.attn = p_attn; a.wo = p_wo; a.m = p_m; a.hidden = p_hidden; a.k0 = p_k0; a.eps = p_eps;
-    const int64_t m0 = (int64_t)blockIdx.x * 32;
-    tfm_ffn_body<WO>(a, m0, min(m0 + 32, a.m), blockIdx.x >> 3);
+    // The tile's segment: its first tile t0, first row r0 and row count rn.  m > 0: one segment from tile 0 (nothing of the table is
+    // read).  Otherwise the batches of a joined flow pass: the workgroup finds its segment from blockIdx.x -- uniform, so scalar compares
+    // and selects (ffn_tile_of in flow_share.h is the same lookup on the host) -- and the body below runs with the rows and the chunk
+    // rotation the tile has when its segment is launched alone.  (One call of the body: one instruction sequence for both.)
+    unsigned t0 = 0;
+    int64_t r0 = 0, rn = p_m;
+    if (p_m <= 0) {
+        r0 = a.seg.row0[0];
+        rn = a.seg.rows[0];
+#pragma unroll
+        for (int i = 1; i < FlowSessionPlan::kSlots; ++i) {
+            const bool in = i < a.seg.n && blockIdx.x >= a.seg.tile0[i];
+            t0 = in ? a.seg.tile0[i] : t0;
+            r0 = in ? a.seg.row0[i] : r0;
+            rn = in ? a.seg.rows[i] : rn;
+        }
+    }
+    const unsigned j = blockIdx.x - t0;
+    const int64_t m0 = r0 + (int64_t)32 * j;
+    tfm_ffn_body<WO>(a, m0, min(m0 + 32, r0 + rn), j >> 3);
 }
 
 }  // namespace astts
@@ -778,9 +799,11 @@ int astts_op_tfm_ffn_fused_supported(int32_t c, int32_t hidden) {
     return c == TF_C && hidden >= 256 && hidden % 256 == 0 && hidden <= 4096 ? 1 : 0;
 }
 
-int astts_op_tfm_ffn_fused(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
-                           int64_t m, int32_t c, int32_t hidden, float eps, const void* attn_f16, const void* wo_frag_f16,
-                           const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
+// One launch for both entry points.  seg == nullptr: rows [0, m) from tile 0.  Otherwise m is the rows of all segments together,
+// `tiles` the launch's tile count, and the kernel is told m = 0: it reads the table.
+static int ffn_fused_launch(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
+                            int64_t m, const FfnSegTable* seg, int64_t tiles, int32_t c, int32_t hidden, float eps, const void* attn_f16,
+                            const void* wo_frag_f16, const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
     ASTTS_REQUIRE(x && w1_frag_f16 && w2_frag_f16 && out, ASTTS_ERR_INVALID, "astts_op_tfm_ffn_fused: null pointer");
     ASTTS_REQUIRE(astts_op_tfm_ffn_fused_supported(c, hidden), ASTTS_ERR_UNSUPPORTED,
                   "astts_op_tfm_ffn_fused: c=%d hidden=%d (channels 256, hidden a multiple of 256 <= 4096)", c, hidden);
@@ -801,18 +824,45 @@ int astts_op_tfm_ffn_fused(const float* x, const void* w1_frag_f16, const float*
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)(32 * TF_AS + 2 * 32 * FF_HS) * sizeof(_Float16) + (size_t)hidden * sizeof(float) + (wo ? 32 * 260 * sizeof(float) : 0);
     TfmFfnArgs a{x, (const _Float16*)w1_frag_f16, b1, (const _Float16*)w2_frag_f16, b2, out, (const _Float16*)attn_f16,
-                 (const _Float16*)wo_frag_f16, bo, m, hidden, k0, eps, nullptr, 0u};
+                 (const _Float16*)wo_frag_f16, bo, seg ? 0 : m, hidden, k0, eps, nullptr, 0u, seg ? *seg : FfnSegTable{}};
+    const dim3 grid((unsigned)(seg ? tiles : (m + 31) / 32));
     static const bool pf_on = !(getenv("ASTTS_TFM_PREFETCH") && atoi(getenv("ASTTS_TFM_PREFETCH")) == 0);
     if (pf_ptr && pf_on) {
         a.pf = (const char*)pf_ptr;
         a.pf_bytes = pf_bytes;
     }
     const bool prof = prof_begin(ASTTS_PROF_GEMM_TILE, st, 4.0 * (double)m * TF_C * hidden + (wo ? 2.0 * (double)m * TF_C * k0 : 0.0));
-    if (wo) hipLaunchKernelGGL(tfm_ffn_fused<true>, dim3((unsigned)((m + 31) / 32)), dim3(512), lds, st, a.x, a.w1, a.attn, a.wo, a.m, a.hidden, a.k0, a.eps, a);
-    else hipLaunchKernelGGL(tfm_ffn_fused<false>, dim3((unsigned)((m + 31) / 32)), dim3(512), lds, st, a.x, a.w1, a.attn, a.wo, a.m, a.hidden, a.k0, a.eps, a);
+    if (wo) hipLaunchKernelGGL(tfm_ffn_fused<true>, grid, dim3(512), lds, st, a.x, a.w1, a.attn, a.wo, a.m, a.hidden, a.k0, a.eps, a);
+    else hipLaunchKernelGGL(tfm_ffn_fused<false>, grid, dim3(512), lds, st, a.x, a.w1, a.attn, a.wo, a.m, a.hidden, a.k0, a.eps, a);
     if (prof) prof_end(ASTTS_PROF_GEMM_TILE, st);
     ASTTS_CHECK_LAUNCH();
     return ASTTS_OK;
+}
+
+int astts_op_tfm_ffn_fused(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
+                           int64_t m, int32_t c, int32_t hidden, float eps, const void* attn_f16, const void* wo_frag_f16,
+                           const float* bo, int32_t k0, const void* pf_ptr, uint32_t pf_bytes, astts_stream_t stream) {
+    return ffn_fused_launch(x, w1_frag_f16, b1, w2_frag_f16, b2, out, m, nullptr, 0, c, hidden, eps, attn_f16, wo_frag_f16, bo, k0, pf_ptr,
+                            pf_bytes, stream);
+}
+
+int astts_op_tfm_ffn_fused_seg(const float* x, const void* w1_frag_f16, const float* b1, const void* w2_frag_f16, const float* b2, float* out,
+                               int32_t n_seg, const int64_t* row0, const int64_t* rows, int32_t c, int32_t hidden, float eps,
+                               const void* attn_f16, const void* wo_frag_f16, const float* bo, int32_t k0, const void* pf_ptr,
+                               uint32_t pf_bytes, astts_stream_t stream) {
+    FfnSegTable seg;
+    const int64_t tiles = ffn_seg_table(n_seg, row0, rows, &seg);
+    ASTTS_REQUIRE(tiles > 0, ASTTS_ERR_INVALID,
+                  "astts_op_tfm_ffn_fused_seg: n_seg=%d (1..%d non-empty row ranges, ascending, without overlap)", n_seg, FlowSessionPlan::kSlots);
+    int64_t m = 0;
+    for (int i = 0; i < n_seg; ++i) m += rows[i];
+    if (n_seg == 1) {      // today's launch, on the segment's rows
+        const size_t r0 = (size_t)row0[0];
+        return ffn_fused_launch(x ? x + r0 * TF_C : x, w1_frag_f16, b1, w2_frag_f16, b2, out ? out + r0 * TF_C : out, m, nullptr, 0, c, hidden, eps,
+                                attn_f16 ? (const _Float16*)attn_f16 + r0 * (size_t)k0 : nullptr, wo_frag_f16, bo, k0, pf_ptr, pf_bytes, stream);
+    }
+    return ffn_fused_launch(x, w1_frag_f16, b1, w2_frag_f16, b2, out, m, &seg, tiles, c, hidden, eps, attn_f16, wo_frag_f16, bo, k0, pf_ptr,
+                            pf_bytes, stream);
 }
 
 /* 1 when astts_op_tfm_attn_fused serves this shape (channels 256, head dim 64, t <= 384), else 0 */

@@ -5,10 +5,12 @@
  * batches of the same frame count can JOIN while earlier ones are still being solved: every launch of a pass then carries the
  * sequences of all admitted batches, each batch at its own Euler step.  The estimator keeps no state between steps except the batch's
  * own x, the time projection and the guidance update are per sequence, and every estimator kernel is per row or per sequence, so a
- * batch's result is bit-identical to astts_flow_solve of that batch alone.  The operators whose launcher chooses a kernel by the
- * total row count (astts_op_gemm, astts_op_groupnorm: a few launches per pass), and astts_op_tfm_ffn_fused, whose order of summation
- * depends on where a row's tile lies in the launch, are issued once per batch over the batch's own rows; the convolutions of the
- * ResNet blocks (astts_op_resnet_conv) and the attention (astts_op_tfm_attn_fused) run once for all batches.
+ * batch's result is bit-identical to astts_flow_solve of that batch alone.  The convolutions of the ResNet blocks
+ * (astts_op_resnet_conv), the attention (astts_op_tfm_attn_fused), the feed-forward launch (astts_op_tfm_ffn_fused_seg: one launch
+ * over a table of the batches' row segments) and every astts_op_gemm of batches whose plans agree (astts_op_gemm_planned) run once
+ * for all batches (astts_flow_share.h; the environment's ASTTS_FLOW_SHARE=0, read per call, issues the last two per batch again).
+ * astts_op_groupnorm, whose grid form depends on the sequence count, the input packing and the guidance + Euler update run once per
+ * batch over the batch's own rows.
  *
  * A session holding one batch issues the launches of astts_flow_solve.  Everything is enqueued on the session's stream and no call
  * waits for the device.  Calls on one session are not thread-safe. */
