@@ -12,7 +12,8 @@ existed); the reference's own values are ``--lr_scheduler linear`` (scripts/trai
 trl's ConstantLengthDataset -- conversations concatenated in file order and cut into chunks of exactly max_seq_len tokens that attend
 across conversation boundaries).  An ``--lr_scheduler`` this command does not know is an error, not a silently constant rate.
 What the reference does and this does not (NF4 base, bf16, gradient checkpointing, embedding resize, multi-GPU): DESIGN.md
-section 2.  The base may be a Llama or a Qwen2 checkpoint directory (src/ft_llm_cn.py's Qwen2.5: q / k / v biases, plain RoPE); its
+section 2.  The base may be a Llama, a Qwen2 (src/ft_llm_cn.py's Qwen2.5: q / k / v biases, plain RoPE) or a Qwen3 checkpoint directory (q / k
+norm; no thinking-mode template is applied, prompts go through as text); its
 config.json decides.
 
 Evaluation while training, checkpoints, the best adapter and resume (the reference's TrainingArguments, src/ft_llm.py:263-291) are

@@ -48,7 +48,7 @@ def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=
     A PEFT LoRA adapter directory (adapter_config.json: what the reference retrieves with) loads over its base checkpoint
     (``base_model_path``, else the adapter's base_model_name_or_path as a local directory or hub-cache snapshot; never fetched) and
     runs LLM.int8 + the unmerged LoRA branch, the reference's numerics; a merged checkpoint runs fp16.  ``precision`` ("int8" /
-    "fp16") overrides either default.  The shape comes from the directory's config.json (Llama or Qwen2; astts.llm.peft.shape_from_config).  Without a directory this raises unless random-init weights are explicitly allowed
+    "fp16") overrides either default.  The shape comes from the directory's config.json (Llama, Qwen2 or Qwen3; astts.llm.peft.shape_from_config).  Without a directory this raises unless random-init weights are explicitly allowed
     (plumbing runs, benchmarks)."""
     import os
 
@@ -67,7 +67,7 @@ def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=
             int8 = (precision or "int8") == "int8"
             return LlamaEmbedder(state, cfg, tokenizer=tok, int8=int8, lora=adapter)
         state = load_llama_weights(model_path)
-        if os.path.isfile(os.path.join(model_path, "config.json")):      # the checkpoint's own shape (Llama or Qwen2); else the 3.2-3B preset
+        if os.path.isfile(os.path.join(model_path, "config.json")):      # the checkpoint's own shape (Llama, Qwen2, Qwen3); else the 3.2-3B preset
             cfg = shape_from_config(model_path, int(state["model.embed_tokens.weight"].shape[0]))
         if (precision or "fp16") == "int8":
             return LlamaEmbedder(state, cfg, tokenizer=tok, int8=True)

@@ -1,6 +1,7 @@
 """Shapes of the embedder LLM.  The reference loads "Llama 3.2" 3B (src/search_milvus.py:251-252, milvus/RAG.py:458:
 hidden 3072 -> 2 x 3072 = the 6144-d bank); these are that checkpoint's config.json values.  The same dataclass describes a Qwen2
-checkpoint (the reference's ``_cn`` scripts run Qwen2.5-7B-Instruct): ``model_type``, ``qkv_bias`` and ``rope_type`` carry the differences."""
+checkpoint (the reference's ``_cn`` scripts run Qwen2.5-7B-Instruct): ``model_type``, ``qkv_bias`` and ``rope_type`` carry the differences.
+A Qwen3 checkpoint adds ``qk_norm`` (a per-head RMSNorm of q and k before RoPE) and a ``head_dim`` that is not hidden / heads."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -27,9 +28,10 @@ class LlamaShape:
     eos_token_id: int = 128001
     bos_token_id: int = 128000
     eos_token_ids: tuple = ()   # further stop ids (generation_config.json's list; set by the adapter loader)
-    model_type: str = "llama"   # "llama" | "qwen2": the transformers class a checkpoint of this shape loads into
+    model_type: str = "llama"   # "llama" | "qwen2" | "qwen3": the transformers class a checkpoint of this shape loads into
     qkv_bias: bool = False      # q / k / v projections carry a bias (Qwen2; Llama's attention_bias)
     rope_type: str = "llama3"   # "llama3": the scaling above; "default": plain 1 / theta^(2i/d), the four rope_* fields unused
+    qk_norm: bool = False       # Qwen3: every q and k head is RMS-normalised over head_dim (self_attn.q_norm / k_norm) before RoPE
 
     @staticmethod
     def llama32_3b() -> "LlamaShape":
@@ -76,8 +78,32 @@ class LlamaShape:
                           max_positions=32768, tie_embeddings=False, eos_token_id=2, bos_token_id=1, model_type="qwen2", qkv_bias=True,
                           rope_type="default")
 
+    @staticmethod
+    def qwen3_tiny() -> "LlamaShape":
+        """Qwen3's differences in their smallest form: the q / k norm, no bias, and 8 / 4 heads of 128 over hidden 640, so that
+        hq = 1024 and hk = 512 both differ from hidden (Qwen3-0.6B: hidden 1024, hq 2048).  Tied head, as 0.6B to 4B."""
+        return LlamaShape(vocab=512, hidden=640, layers=3, heads=8, kv_heads=4, head_dim=128, ffn=1152, rms_eps=1e-6, rope_theta=1e6,
+                          max_positions=32768, tie_embeddings=True, eos_token_id=2, bos_token_id=1, model_type="qwen3", qkv_bias=False,
+                          rope_type="default", qk_norm=True)
+
+    @staticmethod
+    def qwen3_tiny_untied() -> "LlamaShape":
+        """``qwen3_tiny()`` with a head of its own, as Qwen3-8B and up."""
+        from dataclasses import replace
+        return replace(LlamaShape.qwen3_tiny(), tie_embeddings=False)
+
     def hf_config(self):
-        """The transformers config of this shape: Qwen2Config or LlamaConfig (used only by tests/golden/make_qwen2_fixtures.py)."""
+        """The transformers config of this shape: Qwen3Config, Qwen2Config or LlamaConfig (used only by the fixture scripts of tests/golden)."""
+        if self.model_type == "qwen3":
+            from transformers import Qwen3Config
+
+            assert self.qk_norm and self.rope_type == "default", self
+            return Qwen3Config(vocab_size=self.vocab, hidden_size=self.hidden, intermediate_size=self.ffn, num_hidden_layers=self.layers,
+                               num_attention_heads=self.heads, num_key_value_heads=self.kv_heads, head_dim=self.head_dim,
+                               max_position_embeddings=self.max_positions, rms_norm_eps=self.rms_eps, rope_theta=self.rope_theta,
+                               rope_scaling=None, use_sliding_window=False, attention_bias=self.qkv_bias,
+                               tie_word_embeddings=self.tie_embeddings, hidden_act="silu", attention_dropout=0.0,
+                               eos_token_id=self.eos_token_id, bos_token_id=self.bos_token_id, pad_token_id=None)
         if self.model_type == "qwen2":
             from transformers import Qwen2Config
 

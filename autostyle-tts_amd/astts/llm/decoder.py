@@ -12,6 +12,10 @@ No fp16 copy of those projections is kept.  A ``lora`` without ``int8`` is merge
 
 A Qwen2 shape (``cfg.qkv_bias``, ``cfg.rope_type == "default"``, untied head; DESIGN.md section 2 "Qwen2") runs through the same stack:
 the q | k | v bias rides on the fused pack into the GEMM's fp32 epilogue, in both layouts and both precisions.
+
+A Qwen3 shape (``cfg.qk_norm``; DESIGN.md section 2 "Qwen3") differs in one launch per layer: ops.qknorm_rope_ (csrc/ops_qknorm.hip)
+normalises every q and k head over its head_dim values, scales it by ``self_attn.q_norm`` / ``k_norm`` and rotates it, in the launch
+that is RoPE's for the other families.  Its head_dim is a config key of its own: hq = heads * head_dim is not hidden.
 """
 from __future__ import annotations
 
@@ -78,6 +82,15 @@ class LlamaDecoder:
         dropped = [k for k in state if k.endswith(".bias") and not (ok and k.endswith(ok))]
         if dropped:
             raise ValueError(f"the checkpoint has biases that this {cfg.model_type} shape (qkv_bias={cfg.qkv_bias}) does not apply: {dropped[:3]}")
+        # the same rule for Qwen3's q / k norm: weights this shape would not apply are an error, and so are missing ones
+        qkn = [k for k in state if k.endswith((".self_attn.q_norm.weight", ".self_attn.k_norm.weight"))]
+        if qkn and not cfg.qk_norm:
+            raise ValueError(f"the checkpoint has q / k norm weights that this {cfg.model_type} shape (qk_norm=False) does not apply: {sorted(qkn)[:3]}")
+        if cfg.qk_norm:
+            lost = [k for i in range(cfg.layers) for k in (f"model.layers.{i}.self_attn.q_norm.weight", f"model.layers.{i}.self_attn.k_norm.weight")
+                    if k not in state or tuple(state[k].shape) != (cfg.head_dim,)]
+            if lost:
+                raise ValueError(f"this {cfg.model_type} shape has qk_norm=True but the checkpoint lacks [head_dim] norm weights: {lost[:3]}")
         if lora is not None and not self.int8:
             state = _merge_lora(state, lora)
 
@@ -101,6 +114,9 @@ class LlamaDecoder:
             self.L = [{"n1": f(f"model.layers.{i}.input_layernorm.weight"), "n2": f(f"model.layers.{i}.post_attention_layernorm.weight"),
                        "wqkv": weight(i, "self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj"), "wo": weight(i, "self_attn.o_proj"),
                        "wgu": weight(i, "mlp.gate_proj", "mlp.up_proj"), "wd": weight(i, "mlp.down_proj")} for i in range(cfg.layers)]
+            if cfg.qk_norm:
+                for i, L in enumerate(self.L):
+                    L["qn"], L["kn"] = f(f"model.layers.{i}.self_attn.q_norm.weight"), f(f"model.layers.{i}.self_attn.k_norm.weight")
             self.norm = f("model.norm.weight")
             head = state["model.embed_tokens.weight"] if cfg.tie_embeddings else state["lm_head.weight"]
             self.head = ops.PackedWeight(head, None, dev)
@@ -164,11 +180,11 @@ class LlamaDecoder:
     sin = property(lambda self: self._rope[1])
 
     def _layer(self, x: torch.Tensor, L: dict, seg, attend: Callable[[torch.Tensor], torch.Tensor]) -> torch.Tensor:
-        """One decoder layer on the fp32 residual stream ``x``.  ``attend(qkv)``: q|k|v fp16 ``[.., .., hq + 2 hk]`` (not yet rotated) ->
-        the attention output; RoPE, cache and attention are all that the two layouts below differ in."""
+        """One decoder layer on the fp32 residual stream ``x``.  ``attend(qkv, L)``: q|k|v fp16 ``[.., .., hq + 2 hk]`` (not yet rotated) ->
+        the attention output; RoPE (with Qwen3's q / k norm in the same launch), cache and attention are all that the two layouts below differ in."""
         eps = self.cfg.rms_eps                                                    # the norms in fp16: their only consumer is an MFMA operand
         qkv = self._lin(ops.rmsnorm(x, L["n1"], eps), L["wqkv"], seg, out_dtype=torch.float16)
-        x = self._lin(attend(qkv), L["wo"], seg, residual=x)
+        x = self._lin(attend(qkv, L), L["wo"], seg, residual=x)
         gu = self._lin(ops.rmsnorm(x, L["n2"], eps), L["wgu"], seg, out_dtype=torch.float16)
         return self._lin(ops.swiglu(gu), L["wd"], seg, residual=x)
 
@@ -182,8 +198,11 @@ class LlamaDecoder:
         # v_mfma_f32_32x32x16_f16 (csrc/ops_llm.hip attn_gqa_mfma), or the VALU kernel: the second implementation (tests)
         attn = ops.attn_gqa if self.mfma_attention else ops.attn_causal_gqa
 
-        def attend(qkv: torch.Tensor) -> torch.Tensor:                            # [B, T, hq + 2 hk]
-            ops.rope_llama_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)             # q heads then k heads: contiguous
+        def attend(qkv: torch.Tensor, L: dict) -> torch.Tensor:                   # [B, T, hq + 2 hk]
+            if cfg.qk_norm:                                                       # Qwen3: norm and rotation in the one launch
+                ops.qknorm_rope_(qkv, cos, sin, L["qn"], L["kn"], cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.rms_eps)
+            else:
+                ops.rope_llama_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)         # q heads then k heads: contiguous
             return attn(qkv[..., :hq], qkv[..., hq:hq + hk], qkv[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens)
 
         x = ops.embedding(self.embed, ids.to(self.device))
@@ -202,8 +221,12 @@ class LlamaDecoder:
         cos, sin = self._rope_for(cache[0].shape[0])
         hq, hk = cfg.heads * cfg.head_dim, cfg.kv_heads * cfg.head_dim
         for L, kv in zip(self.L, cache):
-            def attend(qkv: torch.Tensor) -> torch.Tensor:                        # [T', B, hq + 2 hk]
-                ops.rope_llama_ex_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim, pos0=pos0, shift=start, time_major=True)
+            def attend(qkv: torch.Tensor, L: dict) -> torch.Tensor:               # [T', B, hq + 2 hk]
+                if cfg.qk_norm:
+                    ops.qknorm_rope_(qkv, cos, sin, L["qn"], L["kn"], cfg.heads, cfg.kv_heads, cfg.head_dim, cfg.rms_eps, pos0=pos0, shift=start,
+                                     time_major=True)
+                else:
+                    ops.rope_llama_ex_(qkv, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim, pos0=pos0, shift=start, time_major=True)
                 kv[pos0:pos0 + tn].copy_(qkv[..., hq:])                            # K (rotated) | V into the cache rows
                 return ops.attn_gqa(qkv[..., :hq], kv[:pos0 + tn, :, :hk], kv[:pos0 + tn, :, hk:], cfg.heads, cfg.kv_heads, cfg.head_dim,
                                     key_start=start, pos0=pos0, time_major=True)

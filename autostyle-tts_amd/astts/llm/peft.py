@@ -172,16 +172,29 @@ class ConfigError(ValueError):
     """A config.json this port refuses to run (and which key says so)."""
 
 
+ARCHITECTURES = {"LlamaForCausalLM": "llama", "Qwen2ForCausalLM": "qwen2", "Qwen3ForCausalLM": "qwen3"}   # transformers class -> model_type
+
+
 def shape_from_config(base_dir: str, vocab: Optional[int] = None) -> LlamaShape:
-    """LlamaShape from a transformers config.json (``vocab``: the row count of the embedding table in use).  ``model_type`` llama or
-    qwen2; RoPE plain (no ``rope_scaling``) or Llama-3 scaled.  Anything that would run but compute another model is refused by key."""
+    """LlamaShape from a transformers config.json (``vocab``: the row count of the embedding table in use).  ``model_type`` llama,
+    qwen2 or qwen3 (full-attention layers only; an absent ``head_dim`` is 128 there, transformers' Qwen3Config default, not hidden / heads);
+    RoPE plain (no ``rope_scaling``) or Llama-3 scaled.  Anything that would run but compute another model is refused by key."""
     with open(os.path.join(base_dir, "config.json")) as f:
         c = json.load(f)
     model_type = str(c.get("model_type", "llama"))
-    if model_type not in ("llama", "qwen2"):
-        raise ConfigError(f"config.json model_type={model_type!r}: only 'llama' and 'qwen2' checkpoints are supported")
+    if model_type not in ("llama", "qwen2", "qwen3"):
+        raise ConfigError(f"config.json model_type={model_type!r}: only 'llama', 'qwen2' and 'qwen3' checkpoints are supported")
+    # the three families differ in tensors, not in shapes (q / k / v biases, q / k norms): a config whose `architectures` names the
+    # class of ANOTHER of them would load that family's weights under this one's rules
+    claimed = sorted({ARCHITECTURES[a] for a in (c.get("architectures") or ()) if a in ARCHITECTURES} - {model_type})
+    if claimed:
+        raise ConfigError(f"config.json model_type={model_type!r} contradicts architectures={c['architectures']} (a {claimed[0]} class): "
+                          "which family's weights the directory holds is not decidable from it")
     if c.get("use_sliding_window"):
         raise ConfigError("config.json use_sliding_window=true: sliding-window attention is not built")
+    other = sorted({str(k) for k in (c.get("layer_types") or ()) if k != "full_attention"})
+    if other:
+        raise ConfigError(f"config.json layer_types contains {other}: only 'full_attention' layers are built")
     if c.get("mlp_bias"):
         raise ConfigError("config.json mlp_bias=true: biases on the MLP projections are not built")
     rp = c.get("rope_parameters") if isinstance(c.get("rope_parameters"), dict) else {}      # transformers >= 5: theta and scaling in one
@@ -195,7 +208,7 @@ def shape_from_config(base_dir: str, vocab: Optional[int] = None) -> LlamaShape:
     eos = c.get("eos_token_id", d.eos_token_id)
     eos_l = list(eos) if isinstance(eos, (list, tuple)) else [eos]
     return LlamaShape(vocab=int(vocab or c["vocab_size"]), hidden=int(c["hidden_size"]), layers=int(c["num_hidden_layers"]), heads=heads,
-                      kv_heads=int(c.get("num_key_value_heads", heads)), head_dim=int(c.get("head_dim") or c["hidden_size"] // heads),
+                      kv_heads=int(c.get("num_key_value_heads", heads)), head_dim=int(c.get("head_dim") or (128 if model_type == "qwen3" else c["hidden_size"] // heads)),
                       ffn=int(c["intermediate_size"]), rms_eps=float(c.get("rms_norm_eps", d.rms_eps)),
                       rope_theta=float(c.get("rope_theta", rp.get("rope_theta", d.rope_theta))), rope_factor=float(rs.get("factor", d.rope_factor)),
                       rope_low_freq_factor=float(rs.get("low_freq_factor", d.rope_low_freq_factor)),
@@ -205,7 +218,7 @@ def shape_from_config(base_dir: str, vocab: Optional[int] = None) -> LlamaShape:
                       tie_embeddings=bool(c.get("tie_word_embeddings", d.tie_embeddings)), eos_token_id=int(eos_l[0]),
                       bos_token_id=int(c.get("bos_token_id", d.bos_token_id) if c.get("bos_token_id") is not None else d.bos_token_id),
                       model_type=model_type, qkv_bias=True if model_type == "qwen2" else bool(c.get("attention_bias", False)),
-                      rope_type=kind)
+                      rope_type=kind, qk_norm=model_type == "qwen3")
 
 
 def generation_eos_ids(base_dir: str) -> Tuple[int, ...]:

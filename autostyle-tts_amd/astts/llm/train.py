@@ -388,7 +388,12 @@ class LoraTrainer:
             h1 = ops.rmsnorm(x, L["n1"], eps)
             qkv, t_qkv = self._fwd(h1, L["wqkv"], G["wqkv"], out_dtype=torch.float16, draw=draw)
             qkv3 = qkv.view(b, t, hq + 2 * hk)
-            ops.rope_llama_(qkv3, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)
+            qk_pre = None
+            if cfg.qk_norm:                                  # Qwen3: backward recomputes the norm from the q | k the op read
+                qk_pre = qkv3[..., :hq + hk].contiguous() if keep else None
+                ops.qknorm_rope_(qkv3, cos, sin, L["qn"], L["kn"], cfg.heads, cfg.kv_heads, cfg.head_dim, eps)
+            else:
+                ops.rope_llama_(qkv3, cos, sin, cfg.heads + cfg.kv_heads, cfg.head_dim)
             ao = ops.attn_gqa(qkv3[..., :hq], qkv3[..., hq:hq + hk], qkv3[..., hq + hk:], cfg.heads, cfg.kv_heads, cfg.head_dim, lens32).view(rows, hq)
             x1, t_o = self._fwd(ao, L["wo"], G["wo"], residual=x, draw=draw)
             h2 = ops.rmsnorm(x1, L["n2"], eps)
@@ -396,7 +401,7 @@ class LoraTrainer:
             act = ops.swiglu(gu)
             x2, t_d = self._fwd(act, L["wd"], G["wd"], residual=x1, draw=draw)
             if keep:
-                saved.append((x, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d))
+                saved.append((x, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d, qk_pre))
             x = x2
         hf = ops.rmsnorm(x, dec.norm, eps)
         targets = next_token_targets(ids, lens32).reshape(rows).contiguous()
@@ -421,14 +426,17 @@ class LoraTrainer:
         dx = torch.zeros((rows, cfg.hidden), dtype=torch.float32, device=self.device)
         tops.rmsnorm_bwd_(dx, dh, xf, dec.norm, eps)
         for L, G, WT, s in zip(reversed(dec.L), reversed(self.G), reversed(self.WT), reversed(saved)):
-            x0, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d = s
+            x0, h1, qkv3, t_qkv, ao, t_o, x1, h2, gu, t_gu, act, t_d, qk_pre = s
             dact = self._bwd(dx, act, t_d, WT["wd"], G["wd"], first, out_dtype=torch.float16, draw=draw)
             dgu = tops.swiglu_bwd(dact, gu)
             dh2 = self._bwd(dgu, h2, t_gu, WT["wgu"], G["wgu"], first, draw=draw)
             tops.rmsnorm_bwd_(dx, dh2, x1, L["n2"], eps)
             dao = self._bwd(dx, ao, t_o, WT["wo"], G["wo"], first, out_dtype=torch.float16, draw=draw)
             dqkv = tops.attn_gqa_bwd(qkv3, dao.view(b, t, hq), cfg.heads, cfg.kv_heads, cfg.head_dim, lens32)
-            ops.rope_llama_(dqkv, cos, nsin, cfg.heads + cfg.kv_heads, cfg.head_dim)          # the rotation's transpose
+            if cfg.qk_norm:                                                                   # rotation and norm transposed in one launch
+                tops.qknorm_rope_bwd_(dqkv, qk_pre, cos, sin, L["qn"], L["kn"], cfg.heads, cfg.kv_heads, cfg.head_dim, eps)
+            else:
+                ops.rope_llama_(dqkv, cos, nsin, cfg.heads + cfg.kv_heads, cfg.head_dim)      # the rotation's transpose
             dh1 = self._bwd(dqkv.view(rows, hq + 2 * hk), h1, t_qkv, WT["wqkv"], G["wqkv"], first, draw=draw)
             tops.rmsnorm_bwd_(dx, dh1, x0, L["n1"], eps)
 

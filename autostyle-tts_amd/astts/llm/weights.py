@@ -12,6 +12,8 @@ from .config import LlamaShape
 
 StateDict = Dict[str, torch.Tensor]
 BIAS_OUTLIERS = (3, 40, 77, 101, 126)    # the entries (mod the bias length) of every q / k bias that make_llama_weights sets to +-16
+# Qwen3 q_norm / k_norm: (entry mod head_dim, value) that make_llama_weights sets in every norm weight.  Real ones have outliers both ways
+QK_NORM_OUTLIERS = ((5, 8.0), (17, 0.02), (33, 0.0), (62, 8.0), (47, 0.02))
 
 
 def make_llama_weights(cfg: LlamaShape, seed: int = 0, device=None) -> StateDict:
@@ -49,6 +51,14 @@ def make_llama_weights(cfg: LlamaShape, seed: int = 0, device=None) -> StateDict
                     for j, at in enumerate(BIAS_OUTLIERS):
                         b[at % n] = 16.0 if (i + j) % 2 == 0 else -16.0
                 sd[p + f"self_attn.{nm}_proj.bias"] = b
+    if cfg.qk_norm:
+        # drawn after everything else, as the biases are: every shape without the norm consumes the generator exactly as before
+        for i in range(cfg.layers):
+            for nm in ("q_norm", "k_norm"):
+                w = 1.0 + r(cfg.head_dim, std=0.1)
+                for at, val in QK_NORM_OUTLIERS:
+                    w[at % cfg.head_dim] = val
+                sd[f"model.layers.{i}.self_attn.{nm}.weight"] = w
     return sd
 
 

@@ -7,6 +7,7 @@ Layout convention: fp32 activations, channels-last ``[B, T, C]`` (or ``[rows, C]
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
 from ctypes import c_float, c_int32, c_int64, c_void_p
 from typing import Optional
@@ -810,6 +811,30 @@ def rope_llama_ex_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, heads:
     assert cos.shape[0] >= pos0 + t and cos.shape[1] == head_dim // 2 and cos.is_contiguous() and sin.is_contiguous()
     _lib.check(_L().astts_op_rope_llama_ex(x.data_ptr(), cos.data_ptr(), sin.data_ptr(), _p(shift), b, t, 1 if time_major else 0, heads,
                                            x.stride(1), head_dim, pos0, _st()))
+    return x
+
+
+@functools.lru_cache(maxsize=None)
+def _qknorm_fn():
+    from . import _lib_llm
+    return _lib_llm.load().astts_op_qknorm_rope
+
+
+def qknorm_rope_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, q_norm_w: torch.Tensor, k_norm_w: torch.Tensor, heads: int,
+                 kv_heads: int, head_dim: int, eps: float, pos0: int = 0, shift: Optional[torch.Tensor] = None,
+                 time_major: bool = False) -> torch.Tensor:
+    """Qwen3's per-head RMSNorm of q and k fused with RoPE (astts_op_qknorm_rope, csrc/ops_qknorm.hip), in place on the first
+    ``(heads + kv_heads) * head_dim`` columns of ``x`` fp16 ``[B, T, ld]`` -- or ``[T, B, ld]`` with ``time_major`` -- in the one launch
+    rope_llama_ / rope_llama_ex_ take: both of their calling forms (``pos0``; ``shift`` int32 ``[B]`` and ``time_major``).  The norm
+    weights are fp32 ``[head_dim]``; v and the row padding are not touched."""
+    assert x.dtype == torch.float16 and x.dim() == 3 and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1)
+    t, b = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
+    assert x.shape[2] >= (heads + kv_heads) * head_dim and cos.shape[0] >= pos0 + t and cos.shape[1] == head_dim // 2 and cos.is_contiguous() \
+        and sin.is_contiguous() and cos.dtype == sin.dtype == q_norm_w.dtype == k_norm_w.dtype == torch.float32
+    assert q_norm_w.shape == k_norm_w.shape == (head_dim,) and q_norm_w.is_cuda and k_norm_w.is_cuda
+    assert shift is None or (shift.dtype == torch.int32 and shift.shape == (b,) and shift.is_cuda)
+    _lib.check(_qknorm_fn()(x.data_ptr(), cos.data_ptr(), sin.data_ptr(), q_norm_w.data_ptr(), k_norm_w.data_ptr(), _p(shift), b, t,
+                            1 if time_major else 0, heads, kv_heads, x.stride(1), head_dim, pos0, eps, _st()))
     return x
 
 

@@ -42,6 +42,26 @@ def attn_gqa_bwd(qkv: torch.Tensor, dout: torch.Tensor, heads: int, kv_heads: in
     return out
 
 
+def qknorm_rope_bwd_(dqkv: torch.Tensor, x_pre: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, q_norm_w: torch.Tensor,
+                     k_norm_w: torch.Tensor, heads: int, kv_heads: int, head_dim: int, eps: float, pos0: int = 0) -> torch.Tensor:
+    """The transpose of ops.qknorm_rope_ (Qwen3), in place on the q | k columns of ``dqkv`` fp16 ``[B, T, ld]`` (d(rotated q | k) as
+    attn_gqa_bwd leaves it -> d(pre-norm q | k)); ``x_pre`` fp16 ``[B, T, >= (heads + kv_heads) * hd]``: the q | k the forward op read.
+    The norm weights are frozen (no weight gradient); dv and the padding are not touched."""
+    wqk = (heads + kv_heads) * head_dim
+    for a in (dqkv, x_pre):
+        assert a.is_cuda and a.dtype == torch.float16 and a.dim() == 3 and a.stride(2) == 1 and a.stride(0) == a.shape[1] * a.stride(1)
+        assert a.shape[2] >= wqk, (a.shape, wqk)
+    b, t = dqkv.shape[0], dqkv.shape[1]
+    assert x_pre.shape[:2] == (b, t)
+    assert cos.shape[0] >= pos0 + t and cos.shape == sin.shape and cos.shape[1] == head_dim // 2 and cos.is_contiguous() and sin.is_contiguous()
+    assert cos.dtype == sin.dtype == torch.float32
+    for w in (q_norm_w, k_norm_w):
+        assert w.is_cuda and w.dtype == torch.float32 and w.shape == (head_dim,) and w.is_contiguous(), (w.dtype, w.shape)
+    check(_L().astts_train_qknorm_rope_bwd(dqkv.data_ptr(), dqkv.stride(1), x_pre.data_ptr(), x_pre.stride(1), cos.data_ptr(), sin.data_ptr(),
+                                           q_norm_w.data_ptr(), k_norm_w.data_ptr(), b, t, heads, kv_heads, head_dim, pos0, float(eps), _st()))
+    return dqkv
+
+
 def rmsnorm_bwd_(dres: torch.Tensor, dy: torch.Tensor, x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
     """``dres += d rmsnorm(x, w) / dx applied to dy``: all fp32, ``[..., c]`` contiguous; the weight is frozen (no dw)."""
     for t in (dres, dy, x, w):

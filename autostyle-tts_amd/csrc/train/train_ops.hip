@@ -5,6 +5,7 @@
 
 #include "philox.h"
 #include "train_common.h"
+#include "../qknorm_lane.h"
 
 namespace astts_train {
 
@@ -214,6 +215,58 @@ __global__ __launch_bounds__(256) void adamw_step(float* __restrict__ p, const f
     v[i] = vv;
 }
 
+// ---- Qwen3 q / k norm + RoPE backward (forward: ../ops_qknorm.hip, lane layout: ../qknorm_lane.h).  In place on the q | k part of dqkv:
+// dy -> the rotation's transpose -> g = w o that; with r and xh = x r recomputed from the kept pre-norm head:  dx = r (g - xh mean(g xh)).
+// xh never comes from the saved output divided by w: w has zeros.
+template <int HD>
+__global__ __launch_bounds__(256) void qknorm_rope_bwd(_Float16* __restrict__ dqkv, int64_t ldd, const _Float16* __restrict__ xpre, int64_t ldx,
+                                                       const float* __restrict__ cs, const float* __restrict__ sn, const float* __restrict__ qw,
+                                                       const float* __restrict__ kw, int64_t units, int t, int heads, int hall, int pos0, float eps) {
+    using namespace astts;
+    constexpr int HALF = HD / 2, LPH = HD / 16;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int sub = (int)(tid & (LPH - 1));
+    const int64_t unit = tid / LPH;
+    const bool live = unit < units;
+    const int64_t u = live ? unit : units - 1;          // the spare lanes repeat the last head and store nothing: full waves for xlane.h
+    const int64_t row = u / hall;
+    const int hd = (int)(u - row * hall);
+    const int pos = pos0 + (int)(row % t);
+
+    _Float16* dp = dqkv + row * ldd + hd * HD + sub * 8;
+    const QknLane d = qkn_load_f16(dp, HALF);
+    const QknLane x = qkn_load_f16(xpre + row * ldx + hd * HD + sub * 8, HALF);
+    float wa[8], wb[8], c[8], s[8];
+    const float* w = (hd < heads ? qw : kw) + sub * 8;
+    qkn_load8_f32(w, wa);
+    qkn_load8_f32(w + HALF, wb);
+    qkn_load8_f32(cs + (int64_t)pos * HALF + sub * 8, c);
+    qkn_load8_f32(sn + (int64_t)pos * HALF + sub * 8, s);
+
+    const float r = qkn_rstd<LPH>(x, eps);
+    QknLane g, xh;
+    float dot = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        g.a[e] = wa[e] * (d.a[e] * c[e] + d.b[e] * s[e]);
+        g.b[e] = wb[e] * (d.b[e] * c[e] - d.a[e] * s[e]);
+        xh.a[e] = x.a[e] * r;
+        xh.b[e] = x.b[e] * r;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dot = fmaf(g.a[e], xh.a[e], dot);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dot = fmaf(g.b[e], xh.b[e], dot);
+    const float m = qkn_group_sum<LPH>(dot) * (1.0f / (float)HD);
+    QknLane o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        o.a[e] = r * (g.a[e] - xh.a[e] * m);
+        o.b[e] = r * (g.b[e] - xh.b[e] * m);
+    }
+    if (live) qkn_store_f16(dp, HALF, o);
+}
+
 }  // namespace astts_train
 
 using namespace astts_train;
@@ -342,6 +395,29 @@ int astts_train_adamw(float* p, const float* g, float* m, float* v, int64_t n, d
     TRAIN_REQUIRE(blocks < (1ll << 31), ASTTS_ERR_INVALID, "adamw: %lld elements exceed the grid", (long long)n);
     hipLaunchKernelGGL(adamw_step, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)(lr * weight_decay), (float)(1.0 - beta1),
                        (float)beta2, (float)(1.0 - beta2), (float)eps, (float)(lr / bias_corr1), (float)sqrt(bias_corr2), (float)grad_mul);
+    TRAIN_CHECK_LAUNCH();
+    return ASTTS_OK;
+}
+
+int astts_train_qknorm_rope_bwd(void* dqkv_f16, int64_t ld_dqkv, const void* x_pre_f16, int64_t ld_x, const float* cos_tab,
+                                const float* sin_tab, const float* q_norm_w, const float* k_norm_w, int32_t b, int32_t t, int32_t heads,
+                                int32_t kv_heads, int32_t head_dim, int32_t pos0, float eps, astts_stream_t stream) {
+    TRAIN_REQUIRE(dqkv_f16 && x_pre_f16 && cos_tab && sin_tab && q_norm_w && k_norm_w, ASTTS_ERR_INVALID, "qknorm_rope_bwd: null pointer");
+    TRAIN_REQUIRE(head_dim == 64 || head_dim == 128, ASTTS_ERR_UNSUPPORTED, "qknorm_rope_bwd: head_dim=%d (built for 64 and 128)", head_dim);
+    const int64_t wqk = (int64_t)(heads + kv_heads) * head_dim;
+    TRAIN_REQUIRE(b >= 1 && t >= 1 && heads >= 1 && kv_heads >= 1 && pos0 >= 0 && ld_dqkv >= wqk && ld_x >= wqk && (ld_dqkv & 7) == 0 &&
+                      (ld_x & 7) == 0 && eps >= 0.0f,
+                  ASTTS_ERR_INVALID, "qknorm_rope_bwd: bad shape b=%d t=%d heads=%d kv_heads=%d head_dim=%d ld_dqkv=%lld ld_x=%lld", b, t, heads,
+                  kv_heads, head_dim, (long long)ld_dqkv, (long long)ld_x);
+    TRAIN_REQUIRE((((uintptr_t)dqkv_f16 | (uintptr_t)x_pre_f16 | (uintptr_t)cos_tab | (uintptr_t)sin_tab | (uintptr_t)q_norm_w |
+                    (uintptr_t)k_norm_w) & 15) == 0,
+                  ASTTS_ERR_INVALID, "qknorm_rope_bwd: the planes, the tables and the norm weights must be 16-byte aligned");
+    const int64_t units = (int64_t)b * t * (heads + kv_heads);
+    const int64_t blocks = cdiv(units * (head_dim / 16), 256);
+    TRAIN_REQUIRE(blocks < (1ll << 31), ASTTS_ERR_INVALID, "qknorm_rope_bwd: %lld heads exceed the grid", (long long)units);
+    const auto kern = head_dim == 64 ? qknorm_rope_bwd<64> : qknorm_rope_bwd<128>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (_Float16*)dqkv_f16, ld_dqkv, (const _Float16*)x_pre_f16,
+                       ld_x, cos_tab, sin_tab, q_norm_w, k_norm_w, units, t, heads, heads + kv_heads, pos0, eps);
     TRAIN_CHECK_LAUNCH();
     return ASTTS_OK;
 }

@@ -124,6 +124,18 @@ int astts_train_lora_dx_dropout(const void* dt_f16, int64_t lddt, const void* at
 int astts_train_lora_merge(const void* w_f16, const float* a, const float* b, void* out_f16, int32_t n, int32_t cin, int32_t n_pad,
                            int32_t cin_pad, int32_t r, int32_t g1, int32_t g2, float scaling, astts_stream_t stream);
 
+/* ---- Qwen3: the transpose of astts_op_qknorm_rope (include/llm/astts_qknorm.h; added under ABI 1), batch-major rows [b, t].
+ * dqkv: fp16 [b * t, ld_dqkv], whose first (heads + kv_heads) * head_dim columns hold d(rotated q | k) as astts_train_attn_gqa_bwd
+ * leaves them; they are overwritten with d(pre-norm q | k), the columns beyond (dv, padding) are not touched.  x_pre: the fp16 q | k
+ * the forward op READ (kept by the trainer), [b * t, ld_x].  Per head, in one pass and in fp32: the rotation's transpose,
+ * g = w o that, r = rsqrt(mean(x^2) + eps) and xh = x r recomputed from x_pre, dx = r (g - xh mean(g xh)), one rounding to fp16.
+ * The norm weights are frozen: no weight gradient.  xh is never recovered from an output divided by w (w may hold zeros).  Fixed-order
+ * sums inside the wave, no atomics: bit-for-bit repeatable.  head_dim 64 or 128 (else ASTTS_ERR_UNSUPPORTED); cos / sin fp32
+ * [>= pos0 + t, head_dim / 2]; all pointers 16-byte aligned, the strides multiples of 8. */
+int astts_train_qknorm_rope_bwd(void* dqkv_f16, int64_t ld_dqkv, const void* x_pre_f16, int64_t ld_x, const float* cos_tab,
+                                const float* sin_tab, const float* q_norm_w, const float* k_norm_w, int32_t b, int32_t t, int32_t heads,
+                                int32_t kv_heads, int32_t head_dim, int32_t pos0, float eps, astts_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
