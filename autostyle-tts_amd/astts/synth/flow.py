@@ -278,23 +278,26 @@ class FlowDecoder:
         ts = 1.0 - torch.cos(torch.linspace(0, 1, n + 1) * 0.5 * math.pi)       # cosine schedule (fp32, as upstream)
         return [float(ts[s]) for s in range(n)], [float(ts[s + 1] - ts[s]) for s in range(n)]
 
+    def _batch_args(self, x, mu, spk_e, cond, lens, tv, dv):
+        """The arguments ``astts_flow_solve`` and ``astts_flow_session_admit`` share: the batch's tensors (checked: contiguous fp32),
+        its shape, the schedule ``tv`` / ``dv`` as C arrays, the guidance rate."""
+        b, t, _ = x.shape
+        assert x.is_contiguous() and mu.is_contiguous() and cond.is_contiguous() and spk_e.is_contiguous()
+        assert x.dtype == mu.dtype == cond.dtype == spk_e.dtype == torch.float32
+        n = len(tv)
+        return (x.data_ptr(), mu.data_ptr(), spk_e.data_ptr(), cond.data_ptr(), None if lens is None else lens.data_ptr(), b, t, n,
+                (ctypes.c_float * n)(*tv), (ctypes.c_float * n)(*dv), self.cfg.cfg_rate)
+
     def solve(self, x: torch.Tensor, mu: torch.Tensor, spk_e: torch.Tensor, cond: torch.Tensor,
               lens: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Euler solve with classifier-free guidance, in place on ``x`` [B, T, mel] (in: noise, out: mel).
         ``lens`` None = fixed-length batch.  Runs in the C++ engine; ``solve_ops`` is the operator-by-operator form."""
         lib = _lib.load()
         eng = self._engine()
-        b, t, _ = x.shape
-        assert x.is_contiguous() and mu.is_contiguous() and cond.is_contiguous() and spk_e.is_contiguous()
-        assert x.dtype == mu.dtype == cond.dtype == spk_e.dtype == torch.float32
-        tv, dv = self._schedule()
-        n = len(tv)
-        need = int(lib.astts_flow_workspace_bytes(eng, b, t))
+        args = self._batch_args(x, mu, spk_e, cond, lens, *self._schedule())
+        need = int(lib.astts_flow_workspace_bytes(eng, x.shape[0], x.shape[1]))
         ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        _lib.check(lib.astts_flow_solve(eng, x.data_ptr(), mu.data_ptr(), spk_e.data_ptr(), cond.data_ptr(),
-                                        None if lens is None else lens.data_ptr(), b, t, n, (ctypes.c_float * n)(*tv),
-                                        (ctypes.c_float * n)(*dv), self.cfg.cfg_rate, ws.data_ptr(), need,
-                                        _lib.stream_ptr()))
+        _lib.check(lib.astts_flow_solve(eng, *args, ws.data_ptr(), need, _lib.stream_ptr()))
         return x
 
     def solve_ops(self, x, mu, spk_e, cond, lens: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -321,14 +324,8 @@ class FlowDecoder:
     def decode(self, tokens, token_lens, prompt_mel, spk, z, mel_total: int) -> torch.Tensor:
         """tokens [B, Tp+Ts], prompt_mel [B, Tm_p, mel], spk [B, spk_dim], z [B, mel_total, mel]
         -> mel [B, mel_total - Tm_p, mel] (fixed-length batch)."""
-        cfg = self.cfg
-        b = tokens.shape[0]
-        mu = self.mu(tokens, token_lens, mel_total)
-        spk_e = ops.linear(torch.nn.functional.normalize(spk, dim=1), self.spk_aff)
-        tmp = prompt_mel.shape[1]
-        cond = torch.zeros((b, mel_total, cfg.mel), dtype=torch.float32, device=self.device)
-        cond[:, :tmp] = prompt_mel
-        x = (self.solve if self.use_engine else self.solve_ops)(z.clone(), mu, spk_e, cond)
+        x, mu, spk_e, cond, tmp = self.prepare(tokens, token_lens, prompt_mel, spk, z, mel_total)
+        x = (self.solve if self.use_engine else self.solve_ops)(x, mu, spk_e, cond)
         return x[:, tmp:].contiguous()
 
     def session(self, t: int, slots: int = 4, rows_max: int = 32, stream=None) -> "FlowSession":
@@ -404,7 +401,7 @@ class FlowSession:
         _lib.check(self._lib.astts_flow_session_create(eng, self.t, self.slots, self.rows_max, len(self._tv), self._ws.data_ptr(), need,
                                                        _lib.stream_ptr(self.stream), ctypes.byref(h)))
         self._h = h
-        self._ctx: List[Optional[FlowJob]] = [None] * 4       # per slot: the job of the batch that holds it
+        self._ctx: List[Optional[FlowJob]] = [None] * self.slots       # per slot: the job of the batch that holds it
 
     def close(self) -> None:
         if self._h is not None:
@@ -429,16 +426,11 @@ class FlowSession:
     def admit(self, x: torch.Tensor, mu: torch.Tensor, spk_e: torch.Tensor, cond: torch.Tensor,
               lens: Optional[torch.Tensor] = None) -> FlowJob:
         """The arguments of ``FlowDecoder.solve``: ``x`` [B, T, mel] (noise) is solved in place."""
-        b, t, _ = x.shape
-        assert x.is_contiguous() and mu.is_contiguous() and cond.is_contiguous() and spk_e.is_contiguous()
-        assert x.dtype == mu.dtype == cond.dtype == spk_e.dtype == torch.float32
-        n = len(self._tv)
-        job = FlowJob(x, mu, spk_e, cond, lens, n)
+        args = self.flow._batch_args(x, mu, spk_e, cond, lens, self._tv, self._dv)
+        job = FlowJob(x, mu, spk_e, cond, lens, len(self._tv))
         slot = ctypes.c_int32(-1)
         with torch.cuda.stream(self.stream):
-            _lib.check(self._lib.astts_flow_session_admit(self._h, x.data_ptr(), mu.data_ptr(), spk_e.data_ptr(), cond.data_ptr(),
-                                                          None if lens is None else lens.data_ptr(), b, t, n, (ctypes.c_float * n)(*self._tv),
-                                                          (ctypes.c_float * n)(*self._dv), self.flow.cfg.cfg_rate, ctypes.byref(slot)))
+            _lib.check(self._lib.astts_flow_session_admit(self._h, *args, ctypes.byref(slot)))
         job.slot = int(slot.value)
         self._ctx[job.slot] = job
         return job

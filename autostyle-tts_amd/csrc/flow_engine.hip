@@ -19,6 +19,7 @@
 #include "../../include/session/astts_flow_share.h"
 
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 struct astts_flow {
@@ -113,8 +114,39 @@ namespace {
 
 constexpr int FLOW_MAX_STEPS = 32;   // Euler steps whose time embeddings / projections are precomputed (the reference runs 10)
 
+// hands out 256-byte aligned pieces of a workspace; base == nullptr only counts (cv.o: the bytes taken so far)
+struct Carver {
+    char* base;
+    size_t o;
+    template <class T>
+    T* take(size_t n) {
+        T* p = base ? (T*)(base + o) : nullptr;
+        o = align_up(o + sizeof(T) * n, 256);
+        return p;
+    }
+};
+
+// where the time path of one batch lives: the rows of `steps` Euler steps x its 2 b sequences
+struct TimeBufs {
+    float *temb0, *temb1, *temb2, *tproj, *tv;
+};
+
+// the one carve of a time path, for a lone solve (FLOW_MAX_STEPS steps, inside carve) and for every slot of a session
+TimeBufs carve_time(Carver& cv, const astts_flow* h, size_t steps, size_t b2) {
+    const astts_flow_config_t& c = h->cfg;
+    const size_t n_res = h->down.size() + h->mid.size() + h->up.size(), trows = steps * b2;
+    TimeBufs T;
+    T.temb0 = cv.take<float>(trows * c.time_in);
+    T.temb1 = cv.take<float>(trows * c.time_dim);
+    T.temb2 = cv.take<float>(trows * c.time_dim);
+    T.tproj = cv.take<float>(n_res * trows * c.channels);
+    T.tv = cv.take<float>(trows);
+    return T;
+}
+
 struct Buffers {
-    float *xin, *r1, *r2, *r3, *pool[6], *temb0, *temb1, *temb2, *tproj, *tv, *d, *up;   // temb* / tproj / tv: all Euler steps at once
+    float *xin, *r1, *r2, *r3, *pool[6], *d, *up;
+    TimeBufs T;     // of a lone solve: all Euler steps at once; T.tproj of a joined pass: the projections gathered by flow_join_assemble
     _Float16 *r1h, *n16, *qkv16, *a16, *f16;
     int *lens_full, *lens_half;
     void* gn_ws;
@@ -122,46 +154,43 @@ struct Buffers {
     float *rstat1, *rstat2;   // astts_op_resnet_conv: per-tile GroupNorm statistics of conv 1 / conv 2
 };
 
-// one carve-up serves astts_flow_workspace_bytes (base == nullptr) and astts_flow_solve
-size_t carve(const astts_flow* h, int b, int t, char* base, Buffers* B) {
+// one carve-up serves astts_flow_workspace_bytes (a counting Carver) and astts_flow_solve
+Buffers carve(Carver& cv, const astts_flow* h, int b, int t) {
     const astts_flow_config_t& c = h->cfg;
     const size_t b2 = 2 * (size_t)b, rows = b2 * t, C = c.channels, hd = (size_t)c.heads * 64;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        void* p = base ? base + o : nullptr;
-        o = align_up(o + bytes, 256);
-        return p;
-    };
     const size_t in_ch = 4 * (size_t)c.mel > 2 * C ? 4 * (size_t)c.mel : 2 * C;
-    Buffers tmp;
-    Buffers& X = B ? *B : tmp;
-    X.xin = (float*)take(sizeof(float) * rows * in_ch);
-    X.r1 = (float*)take(sizeof(float) * rows * C);
-    X.r2 = (float*)take(sizeof(float) * rows * C);
-    X.r3 = (float*)take(sizeof(float) * rows * C);
-    for (int i = 0; i < 6; ++i) X.pool[i] = (float*)take(sizeof(float) * rows * C);
-    X.up = (float*)take(sizeof(float) * b2 * ((size_t)t + 4) * 2 * C);
-    X.r1h = (_Float16*)take(sizeof(_Float16) * rows * C);
-    X.n16 = (_Float16*)take(sizeof(_Float16) * rows * C);
-    X.qkv16 = (_Float16*)take(sizeof(_Float16) * rows * 3 * hd);
-    X.a16 = (_Float16*)take(sizeof(_Float16) * rows * hd);
-    X.f16 = (_Float16*)take(sizeof(_Float16) * rows * 4 * C);
+    Buffers X;
+    X.xin = cv.take<float>(rows * in_ch);
+    X.r1 = cv.take<float>(rows * C);
+    X.r2 = cv.take<float>(rows * C);
+    X.r3 = cv.take<float>(rows * C);
+    for (int i = 0; i < 6; ++i) X.pool[i] = cv.take<float>(rows * C);
+    X.up = cv.take<float>(b2 * ((size_t)t + 4) * 2 * C);
+    X.r1h = cv.take<_Float16>(rows * C);
+    X.n16 = cv.take<_Float16>(rows * C);
+    X.qkv16 = cv.take<_Float16>(rows * 3 * hd);
+    X.a16 = cv.take<_Float16>(rows * hd);
+    X.f16 = cv.take<_Float16>(rows * 4 * C);
     // the time path does not depend on x: it is evaluated for ALL Euler steps before the first one (FLOW_MAX_STEPS rows blocks)
-    const size_t n_res = h->down.size() + h->mid.size() + h->up.size();
-    X.temb0 = (float*)take(sizeof(float) * FLOW_MAX_STEPS * b2 * c.time_in);
-    X.temb1 = (float*)take(sizeof(float) * FLOW_MAX_STEPS * b2 * c.time_dim);
-    X.temb2 = (float*)take(sizeof(float) * FLOW_MAX_STEPS * b2 * c.time_dim);
-    X.tproj = (float*)take(sizeof(float) * n_res * FLOW_MAX_STEPS * b2 * C);
-    X.tv = (float*)take(sizeof(float) * FLOW_MAX_STEPS * b2);
-    X.d = (float*)take(sizeof(float) * rows * c.mel);
-    X.lens_full = (int*)take(sizeof(int) * b2);
-    X.lens_half = (int*)take(sizeof(int) * b2);
+    X.T = carve_time(cv, h, FLOW_MAX_STEPS, b2);
+    X.d = cv.take<float>(rows * c.mel);
+    X.lens_full = cv.take<int>(b2);
+    X.lens_half = cv.take<int>(b2);
     X.gn_ws_bytes = astts_op_groupnorm_workspace_bytes((int)b2, t, c.groups);
-    X.gn_ws = take(X.gn_ws_bytes > 16 ? X.gn_ws_bytes : 16);
-    X.rstat1 = (float*)take(sizeof(float) * astts_op_resnet_conv_stats_floats((int32_t)b2, t));
-    X.rstat2 = (float*)take(sizeof(float) * astts_op_resnet_conv_stats_floats((int32_t)b2, t));
-    return o;
+    X.gn_ws = cv.take<char>(X.gn_ws_bytes > 16 ? X.gn_ws_bytes : 16);
+    X.rstat1 = cv.take<float>(astts_op_resnet_conv_stats_floats((int32_t)b2, t));
+    X.rstat2 = cv.take<float>(astts_op_resnet_conv_stats_floats((int32_t)b2, t));
+    return X;
 }
+
+// does this ResNet block take the three-launch path (astts_op_resnet_conv)?  Ctx::resnet and the prefetch hint of the mid loop ask here
+bool resnet_fused(const astts_flow_resnet_t& r, int groups) {
+    auto served = [&](const astts_weight_t& w) { return astts_op_resnet_conv_supported(w.cin, w.n, groups, w.taps) != 0; };
+    return r.c1_frag && r.c2_frag && r.res_frag && served(r.c1) && served(r.c2) && served(r.res);
+}
+
+// bytes of a weight's fp16 image (row-major or fragment order: the same count), as a prefetch hint's length
+uint32_t weight_bytes(const astts_weight_t& w) { return (uint32_t)((size_t)w.n * w.taps * w.cin_pad * 2); }
 
 // one batch's share of an estimator pass: its own tensors, its sequences [seq0, seq0 + 2 b) of the pass, its Euler step
 struct Seg {
@@ -172,19 +201,22 @@ struct Seg {
 };
 
 struct Ctx {
-    const astts_flow* h;
-    Buffers B;
-    int b2, T;          // b2: sequences of the pass (all batches')
-    bool full;
-    astts_stream_t st;
-    const Seg* seg;     // the batches of the pass, one after the other without gaps; astts_flow_solve: one
-    int n_seg;
-    bool share;         // a joined pass issues ONE feed-forward launch and one GEMM launch per group of equal plans (flow_share.h)
+    const astts_flow* const h;
+    const Buffers B;
+    const int b2, T;    // b2: sequences of the pass (all batches')
+    const bool full;    // no sequence is shorter than T: the length masks are not launched
+    const astts_stream_t st;
+    const Seg* const seg;   // the batches of the pass, one after the other without gaps; astts_flow_solve: one
+    const int n_seg;
+    const bool share;   // a joined pass issues ONE feed-forward launch and one GEMM launch per group of equal plans (flow_share.h)
 
-    int gemm1(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
-              int t_in, int t_out, int stride, int pad, int act) const {
-        return astts_op_gemm(x, x16, w.w, w.bias, residual, nullptr, out, out16, m, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
-                             residual ? w.n : 0, t_in, t_out, stride, 1, pad, act, 1.0f, 0.1f, nullptr, st);
+    Ctx(const astts_flow* h, const Buffers& B, int t, bool full, astts_stream_t st, const Seg* seg, int n_seg, bool share)
+        : h(h), B(B), b2(seg[n_seg - 1].seq0 + 2 * seg[n_seg - 1].b), T(t), full(full), st(st), seg(seg), n_seg(n_seg), share(share) {}
+
+    // a plain projection of `rows` rows, one launch whatever the pass carries (the time path)
+    int linear(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t rows, int act) const {
+        return astts_op_gemm(x, x16, w.w, w.bias, residual, nullptr, out, out16, rows, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
+                             residual ? w.n : 0, (int)rows, (int)rows, 1, 1, 0, act, 1.0f, 0.1f, nullptr, st);
     }
     // a convolution over all sequences ([b2, t_in, cin] -> [b2, t_out, n]).  launch_gemm plans kernel family and tile from the row count
     // (gemm_plan.h), and a row's sum depends on the kernel, not on where its tile lies.  A joined pass therefore groups consecutive
@@ -193,10 +225,10 @@ struct Ctx {
     // family, stay separate.  So does every GEMM with an activation: the epilogue of a tile that lies wholly inside the output evaluates
     // GELU with gelu_erf_fast, the epilogue of an edge tile with erff (gemm_kernels.h), so a batch's last rows would change their bits when
     // another batch's rows complete their tile (the unfused feed-forward's W1; found by the tiny-width session tests).
-    // `per_seq`: false = a projection of rows (t_in == t_out == the launch's row count, as linear()).
-    int gemm(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m,
-             int t_in, int t_out, int stride, int pad, int act, bool per_seq = true) const {
-        if (n_seg == 1) return gemm1(x, x16, w, residual, out, out16, m, per_seq ? t_in : (int)m, per_seq ? t_out : (int)m, stride, pad, act);
+    // A lone batch is one group planned by its own row count: the launch of astts_op_gemm.
+    // `rows_as_one`: a projection of rows (proj()), which a launch takes as ONE sequence of all its rows.
+    int gemm(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int t_in, int t_out, int stride,
+             int pad, int act, bool rows_as_one = false) const {
         int64_t rows[FlowSessionPlan::kSlots];
         for (int i = 0; i < n_seg; ++i) rows[i] = 2 * (int64_t)seg[i].b * t_out;
         const GemmGroups G = gemm_share_groups(gemm_shape_of_call(x, x16, out16, w.n, w.cin, w.cin_pad, w.taps, w.cin, t_in, t_out, stride, pad),
@@ -205,19 +237,16 @@ struct Ctx {
             const int64_t s0 = seg[G.first[g]].seq0;
             int64_t gm = 0;
             for (int i = 0; i < G.count[g]; ++i) gm += rows[G.first[g] + i];
-            const int ti = per_seq ? t_in : (int)gm, to = per_seq ? t_out : (int)gm;
+            const int ti = rows_as_one ? (int)gm : t_in, to = rows_as_one ? (int)gm : t_out;
             RUN(astts_op_gemm_planned((const char*)x + s0 * t_in * w.cin * (x16 ? 2 : 4), x16, w.w, w.bias, residual ? residual + s0 * t_out * w.n : nullptr,
                                       nullptr, (char*)out + s0 * t_out * w.n * (out16 ? 2 : 4), out16, gm, w.n, w.cin, w.cin_pad, w.taps, w.cin, w.n,
                                       residual ? w.n : 0, ti, to, stride, 1, pad, act, 1.0f, 0.1f, nullptr, G.plan_m[g], st));
         }
         return ASTTS_OK;
     }
-    int linear(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int64_t m, int act) const {
-        return gemm1(x, x16, w, residual, out, out16, m, (int)m, (int)m, 1, 0, act);
-    }
     // a projection of the rows of all sequences ([b2 * t, cin] -> [b2 * t, n]): grouped by plan in a joined pass, as gemm()
-    int linear_seq(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int t, int act) const {
-        return gemm(x, x16, w, residual, out, out16, (int64_t)b2 * t, t, t, 1, 0, act, false);
+    int proj(const void* x, int x16, const astts_weight_t& w, const float* residual, void* out, int out16, int t, int act) const {
+        return gemm(x, x16, w, residual, out, out16, t, t, 1, 0, act, true);
     }
     // the rows of every batch of the pass at t frames per sequence, for the segmented feed-forward launch
     void seg_rows(int t, int64_t* row0, int64_t* rows) const {
@@ -230,10 +259,9 @@ struct Ctx {
     int gnorm(const float* x, const int* lens, const float* gw, const float* gb, const float* add_bc, void* y, int y16, int t) const {
         const int C = h->cfg.channels, G = h->cfg.groups;
         for (int i = 0; i < n_seg; ++i) {
-            const int64_t s0 = n_seg == 1 ? 0 : seg[i].seq0;
-            const int nb = n_seg == 1 ? b2 : 2 * seg[i].b;
+            const int64_t s0 = seg[i].seq0;
             RUN(astts_op_groupnorm(x + s0 * t * C, lens + s0, gw, gb, add_bc ? add_bc + s0 * C : nullptr, (char*)y + s0 * t * C * (y16 ? 2 : 4),
-                                   y16, nb, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
+                                   y16, 2 * seg[i].b, t, C, G, 1e-5f, 1, B.gn_ws, B.gn_ws_bytes, st));
         }
         return ASTTS_OK;
     }
@@ -242,30 +270,29 @@ struct Ctx {
         return astts_op_elementwise(ASTTS_EL_MUL_ROWMASK, x, nullptr, nullptr, lens, x, (int64_t)b2 * t * c, t, c, 0.0f, 0.0f, st);
     }
 
+    // the q|k|v image of one transformer block
+    uint32_t qkv_bytes() const { return 3u * (uint32_t)h->cfg.heads * 64u * (uint32_t)h->cfg.channels * 2u; }
+
     // ResnetBlock1D on x [b2, t, cin] (already masked) -> out [b2, t, C]
     // `tproj` [b2, C]: this block's time projection for the current Euler step (precomputed for all steps by astts_flow_solve)
     // `next_w` / `next_bytes`: the weight image the launch after this block reads first (its first transformer block's q|k|v image)
     int resnet(const astts_flow_resnet_t& r, const float* tproj, const float* x, const int* lens, int t, float* out,
                const void* next_w = nullptr, uint32_t next_bytes = 0) const {
-        const int G = h->cfg.groups;
-        const int64_t rows = (int64_t)b2 * t;
-        if (r.c1_frag && r.c2_frag && r.res_frag && astts_op_resnet_conv_supported(r.c1.cin, r.c1.n, G, r.c1.taps) &&
-            astts_op_resnet_conv_supported(r.c2.cin, r.c2.n, G, r.c2.taps) && astts_op_resnet_conv_supported(r.res.cin, r.res.n, G, r.res.taps)) {
+        if (resnet_fused(r, h->cfg.groups)) {
             // three launches, GroupNorm + Mish folded into the convolutions (ops_resnet_conv.hip)
             // every launch requests the NEXT one's (cold) weights into L2 while it runs
-            auto wbytes = [](const astts_weight_t& w) { return (uint32_t)((size_t)w.n * w.taps * w.cin_pad * 2); };
             RUN(astts_op_resnet_conv(x, r.c1_frag, r.c1.bias, B.r1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                     B.rstat1, lens, b2, t, r.c1.cin, r.c1.taps, 1e-5f, r.c2_frag, wbytes(r.c2), st));
+                                     B.rstat1, lens, b2, t, r.c1.cin, r.c1.taps, 1e-5f, r.c2_frag, weight_bytes(r.c2), st));
             RUN(astts_op_resnet_conv(B.r1, r.c2_frag, r.c2.bias, B.r2, B.rstat1, r.g1_w, r.g1_b, tproj, nullptr, nullptr, nullptr, nullptr,
-                                     B.rstat2, lens, b2, t, r.c2.cin, r.c2.taps, 1e-5f, r.res_frag, wbytes(r.res), st));
+                                     B.rstat2, lens, b2, t, r.c2.cin, r.c2.taps, 1e-5f, r.res_frag, weight_bytes(r.res), st));
             return astts_op_resnet_conv(x, r.res_frag, r.res.bias, out, nullptr, nullptr, nullptr, nullptr, B.r2, B.rstat2, r.g2_w, r.g2_b,
                                         nullptr, lens, b2, t, r.res.cin, r.res.taps, 1e-5f, next_w, next_bytes, st);
         }
-        RUN(gemm(x, 0, r.c1, nullptr, B.r1, 0, rows, t, t, 1, 1, ASTTS_ACT_NONE));
+        RUN(gemm(x, 0, r.c1, nullptr, B.r1, 0, t, t, 1, 1, ASTTS_ACT_NONE));
         RUN(gnorm(B.r1, lens, r.g1_w, r.g1_b, tproj, B.r1h, 1, t));
-        RUN(gemm(B.r1h, 1, r.c2, nullptr, B.r2, 0, rows, t, t, 1, 1, ASTTS_ACT_NONE));
+        RUN(gemm(B.r1h, 1, r.c2, nullptr, B.r2, 0, t, t, 1, 1, ASTTS_ACT_NONE));
         RUN(gnorm(B.r2, lens, r.g2_w, r.g2_b, nullptr, B.r3, 0, t));
-        return gemm(x, 0, r.res, B.r3, out, 0, rows, t, t, 1, 0, ASTTS_ACT_NONE);     // res_conv(x) + h
+        return gemm(x, 0, r.res, B.r3, out, 0, t, t, 1, 0, ASTTS_ACT_NONE);     // res_conv(x) + h
     }
 
     // BasicTransformerBlock: x (in p) -> result back in p, q is scratch of the same size
@@ -274,10 +301,7 @@ struct Ctx {
     int tfm(const astts_flow_tfm_t& w, float* p, float* q, const int* lens, int t, const void* next_w = nullptr, uint32_t next_bytes = 0) const {
         const int C = h->cfg.channels, heads = h->cfg.heads, hd = heads * 64;
         const int64_t rows = (int64_t)b2 * t;
-        // ASTTS_FLOW_UNFUSED_ATTN_MIN_ROWS=n (experiment): at >= n rows the attention half runs as LayerNorm + one q|k|v GEMM + the flash kernel
-        static const int64_t unfused_min = exp_env_int("ASTTS_FLOW_UNFUSED_ATTN_MIN_ROWS", 0);
-        const bool fused_attn = w.qkv_frag && astts_op_tfm_attn_fused_supported(C, heads, t) && !(unfused_min > 0 && rows >= unfused_min);
-        if (fused_attn) {      // LayerNorm + q|k|v + attention in one launch (ops_tfm_fused.hip)
+        if (w.qkv_frag && astts_op_tfm_attn_fused_supported(C, heads, t)) {      // LayerNorm + q|k|v + attention in one launch (ops_tfm_fused.hip)
             // the feed-forward launch that follows streams 1.25 MB of weights no launch has touched since the last Euler step:
             // requested into L2 from here
             const void* pf[3] = {w.wo_frag, w.w1_frag, w.w2_frag};
@@ -286,7 +310,7 @@ struct Ctx {
                                         (w.wo_frag && w.w1_frag && w.w2_frag) ? 3 : 0, st));
         } else {
             RUN(astts_op_layernorm(p, w.n1_w, w.n1_b, B.n16, 1, rows, C, C, C, 1e-5f, 0.0f, st));
-            RUN(linear_seq(B.n16, 1, w.qkv, nullptr, B.qkv16, 1, t, ASTTS_ACT_NONE));
+            RUN(proj(B.n16, 1, w.qkv, nullptr, B.qkv16, 1, t, ASTTS_ACT_NONE));
             RUN(astts_op_attn_mha(B.qkv16, B.qkv16 + hd, B.qkv16 + 2 * hd, 1, lens, B.a16, 1, b2, heads, t, 3 * hd, 3 * hd, hd,
                                   0.125f, st));
         }
@@ -300,19 +324,16 @@ struct Ctx {
         // What stays per batch in a joined pass: astts_op_groupnorm (its grid form depends on the sequence count; three launches per
         // pass), flow_pack_input and the CFG-Euler update (each batch's own tensors), and GEMMs whose plans differ (gemm()).
         const bool ffn_wo = ffn && w.wo_frag && (hd == 256 || hd == 512);
-        if (!ffn_wo) RUN(linear_seq(B.a16, 1, w.wo, p, q, 0, t, ASTTS_ACT_NONE));
+        if (!ffn_wo) RUN(proj(B.a16, 1, w.wo, p, q, 0, t, ASTTS_ACT_NONE));
         if (ffn) {    // (output projection + residual +) LayerNorm + W1 + GELU + W2 + residual: one launch, in place on p with the projection
             const float* in = ffn_wo ? p : q;
             const _Float16* attn = ffn_wo ? B.a16 : nullptr;
             const void* wo = ffn_wo ? w.wo_frag : nullptr;
             const float* bo = ffn_wo ? w.wo.bias : nullptr;
             const int k0 = ffn_wo ? hd : 0;
-            if (n_seg == 1)
-                return astts_op_tfm_ffn_fused(in, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, rows, C, w.w1.n, 1e-5f, attn, wo, bo, k0,
-                                              ffn_wo ? next_w : nullptr, ffn_wo ? next_bytes : 0u, st);
             int64_t row0[FlowSessionPlan::kSlots], nrows[FlowSessionPlan::kSlots];
             seg_rows(t, row0, nrows);
-            if (share)
+            if (share && n_seg > 1)
                 return astts_op_tfm_ffn_fused_seg(in, w.w1_frag, w.w1.bias, w.w2_frag, w.w2.bias, p, n_seg, row0, nrows, C, w.w1.n, 1e-5f, attn, wo,
                                                   bo, k0, ffn_wo ? next_w : nullptr, ffn_wo ? next_bytes : 0u, st);
             for (int i = 0; i < n_seg; ++i) {
@@ -323,8 +344,21 @@ struct Ctx {
             return ASTTS_OK;
         }
         RUN(astts_op_layernorm(q, w.n3_w, w.n3_b, B.n16, 1, rows, C, C, C, 1e-5f, 0.0f, st));
-        RUN(linear_seq(B.n16, 1, w.w1, nullptr, B.f16, 1, t, ASTTS_ACT_GELU));
-        return linear_seq(B.f16, 1, w.w2, q, p, 0, t, ASTTS_ACT_NONE);
+        RUN(proj(B.n16, 1, w.w1, nullptr, B.f16, 1, t, ASTTS_ACT_GELU));
+        return proj(B.f16, 1, w.w2, q, p, 0, t, ASTTS_ACT_NONE);
+    }
+
+    // One U-Net block: ResNet `in` -> `out` (never in place: every GEMM block reads whole input rows), the transformer chain on `out`
+    // with `scratch` of the same size, the length mask.  Every launch chain prefetches what follows it: the ResNet the first transformer
+    // block's q|k|v image, every transformer block the next one's, the last one `next_w` / `next_bytes` (what the caller runs next).
+    int block(const astts_flow::Block& blk, const float* tproj, const float* in, float* out, float* scratch, const int* lens, int t,
+              const void* next_w = nullptr, uint32_t next_bytes = 0) const {
+        RUN(resnet(blk.res, tproj, in, lens, t, out, blk.tfm.empty() ? nullptr : blk.tfm[0].qkv_frag, qkv_bytes()));
+        for (size_t ti = 0; ti < blk.tfm.size(); ++ti) {
+            const bool more = ti + 1 < blk.tfm.size();
+            RUN(tfm(blk.tfm[ti], out, scratch, lens, t, more ? blk.tfm[ti + 1].qkv_frag : next_w, more ? qkv_bytes() : next_bytes));
+        }
+        return mask(out, lens, t, h->cfg.channels);
     }
 };
 
@@ -370,26 +404,24 @@ int astts_flow_destroy(astts_flow_t* h) {
 
 size_t astts_flow_workspace_bytes(const astts_flow_t* h, int32_t b, int32_t t) {
     if (!h || b < 1 || t < 1) return 0;
-    return carve(h, b, t, nullptr, nullptr);
+    Carver cv{nullptr, 0};
+    carve(cv, h, b, t);
+    return cv.o;
 }
 
 }  // extern "C"
 
 namespace {
 
-// where the time path of one batch lives: the rows of `steps` Euler steps x its 2 b sequences
-struct TimeBufs {
-    float *tv, *temb0, *temb1, *temb2, *tproj;
-};
-
-// The time path of `steps` Euler steps of one batch of b2 sequences, hoisted out of the dependent chain (it depends on the schedule
+// The time path of `steps` Euler steps of the pass's one batch, hoisted out of the dependent chain (it depends on the schedule
 // only): time embedding -> MLP -> Mish (every ResnetBlock1D applies Mish before its own projection) for all steps x b2 rows in one
 // pass, then ONE projection GEMM per ResNet block over all steps: ~20 launches per solve instead of 21 per step.
 // -> T.tproj [ResNet block][steps * b2][C]
-int time_path(const Ctx& k, const TimeBufs& T, const float* t_host, int steps, int b2) {
+int time_path(const Ctx& k, const TimeBufs& T, const float* t_host, int steps) {
     const astts_flow* h = k.h;
     const astts_flow_config_t& c = h->cfg;
     hipStream_t st = (hipStream_t)k.st;
+    const int b2 = k.b2;
     const int64_t trows = (int64_t)steps * b2;
     for (int j = 0; j < steps; ++j) {
         hipLaunchKernelGGL(flow_fill_time, dim3((b2 + 63) / 64), dim3(64), 0, st, T.tv + (size_t)j * b2, t_host[j], b2);
@@ -416,122 +448,91 @@ int estimator_pass(const Ctx& k, const float* tproj, size_t tproj_stride, const 
     const Buffers& B = k.B;
     const int b2 = k.b2, t = k.T, C = c.channels, mel = c.mel;
     const int t_half = (t - 1) / 2 + 1;     // conv k=3, stride 2, pad 1
-      {
-        size_t ri = 0;      // ResNet block counter of this estimator pass (down, mid, up order: the order of the table above)
-        auto tproj_of = [&]() { return tproj + (ri++) * tproj_stride; };
-        for (int i = 0; i < k.n_seg; ++i) {
-            const Seg& g = k.seg[i];
-            hipLaunchKernelGGL(flow_pack_input, dim3(grid_for((int64_t)2 * g.b * t * 4 * mel)), dim3(256), 0, st, g.x, g.mu, g.spk, g.cond,
-                               lens_full + g.seq0, B.xin + (size_t)g.seq0 * t * 4 * mel, g.b, t, mel);
-            ASTTS_CHECK_LAUNCH();
-        }
+    size_t ri = 0;      // ResNet block counter of this estimator pass (down, mid, up order: the order of the table above)
+    auto tproj_of = [&]() { return tproj + (ri++) * tproj_stride; };
+    for (int i = 0; i < k.n_seg; ++i) {
+        const Seg& g = k.seg[i];
+        hipLaunchKernelGGL(flow_pack_input, dim3(grid_for((int64_t)2 * g.b * t * 4 * mel)), dim3(256), 0, st, g.x, g.mu, g.spk, g.cond,
+                           lens_full + g.seq0, B.xin + (size_t)g.seq0 * t * 4 * mel, g.b, t, mel);
+        ASTTS_CHECK_LAUNCH();
+    }
 
-        // buffer pool: cur / other ping-pong for the residual stream, the rest become skips
-        float* pool[6];
-        for (int i = 0; i < 6; ++i) pool[i] = B.pool[i];
-        int n_free = 6;
-        auto grab = [&]() { return pool[--n_free]; };
-        float* cur = grab();
-        float* other = grab();
-        float* skips[4];
-        int skip_t[4];
-        const int* skip_lens[4];
-        int n_skips = 0;
-        const float* block_in = B.xin;
-        int tt = t;
-        const int* L = lens_full;
+    // buffer pool: cur / other ping-pong for the residual stream, the rest become skips
+    float* pool[6];
+    for (int i = 0; i < 6; ++i) pool[i] = B.pool[i];
+    int n_free = 6;
+    auto grab = [&]() { return pool[--n_free]; };
+    float* cur = grab();
+    float* other = grab();
+    float* skips[4];
+    int skip_t[4];
+    const int* skip_lens[4];
+    int n_skips = 0;
+    const float* block_in = B.xin;
+    int tt = t;
+    const int* L = lens_full;
 
-        const uint32_t qkv_bytes = 3u * (uint32_t)c.heads * 64u * (uint32_t)C * 2u;     // one block's q|k|v image
-        for (size_t i = 0; i < h->down.size(); ++i) {
-            const astts_flow::Block& blk = h->down[i];
-            RUN(k.resnet(blk.res, tproj_of(), block_in, L, tt, other, blk.tfm.empty() ? nullptr : blk.tfm[0].qkv_frag, qkv_bytes));     // never in place: every GEMM block reads whole input rows
-            { float* sw = cur; cur = other; other = sw; }
-            for (size_t ti = 0; ti < blk.tfm.size(); ++ti) {
-                const bool more = ti + 1 < blk.tfm.size();
-                RUN(k.tfm(blk.tfm[ti], cur, other, L, tt, more ? blk.tfm[ti + 1].qkv_frag : nullptr,
-                          more ? (uint32_t)(3u * (uint32_t)c.heads * 64u * (uint32_t)C * 2u) : 0u));
-            }
-            RUN(k.mask(cur, L, tt, C));
-            skips[n_skips] = cur;
-            skip_t[n_skips] = tt;
-            skip_lens[n_skips] = L;
-            ++n_skips;
-            float* nxt = other;
-            other = grab();
-            if (blk.kind == ASTTS_FLOW_RESAMPLE_DOWN) {
-                RUN(k.gemm(cur, 0, blk.resample, nullptr, nxt, 0, (int64_t)b2 * t_half, tt, t_half, 2, 1, ASTTS_ACT_NONE));
-                tt = t_half;
-                L = lens_half;
-            } else {
-                RUN(k.gemm(cur, 0, blk.resample, nullptr, nxt, 0, (int64_t)b2 * tt, tt, tt, 1, 1, ASTTS_ACT_NONE));
-            }
-            cur = nxt;
-            RUN(k.mask(cur, L, tt, C));
-            block_in = cur;
+    for (const astts_flow::Block& blk : h->down) {
+        RUN(k.block(blk, tproj_of(), block_in, other, cur, L, tt));
+        skips[n_skips] = other;
+        skip_t[n_skips] = tt;
+        skip_lens[n_skips] = L;
+        ++n_skips;
+        const float* skip = other;
+        other = grab();
+        if (blk.kind == ASTTS_FLOW_RESAMPLE_DOWN) {
+            RUN(k.gemm(skip, 0, blk.resample, nullptr, cur, 0, tt, t_half, 2, 1, ASTTS_ACT_NONE));
+            tt = t_half;
+            L = lens_half;
+        } else {
+            RUN(k.gemm(skip, 0, blk.resample, nullptr, cur, 0, tt, tt, 1, 1, ASTTS_ACT_NONE));
         }
-        for (size_t mi = 0; mi < h->mid.size(); ++mi) {
-            const astts_flow::Block& blk = h->mid[mi];
-            RUN(k.resnet(blk.res, tproj_of(), cur, L, tt, other, blk.tfm.empty() ? nullptr : blk.tfm[0].qkv_frag, qkv_bytes));
-            float* sw = cur; cur = other; other = sw;
-            for (size_t ti = 0; ti < blk.tfm.size(); ++ti) {
-                const bool more = ti + 1 < blk.tfm.size();
-                // after the last transformer block of a mid block comes the next mid block's first convolution
-                // (its fragment-order image when that ResNet block takes the three-launch path, else the row-major one)
-                const astts_flow_resnet_t* nr = (!more && mi + 1 < h->mid.size()) ? &h->mid[mi + 1].res : nullptr;
-                const astts_weight_t* nc = nr ? &nr->c1 : nullptr;
-                const void* nw = !nr ? nullptr
-                                 : (nr->c1_frag && nr->c2_frag && nr->res_frag && astts_op_resnet_conv_supported(nc->cin, nc->n, c.groups, nc->taps) &&
-                                    astts_op_resnet_conv_supported(nr->c2.cin, nr->c2.n, c.groups, nr->c2.taps) &&
-                                    astts_op_resnet_conv_supported(nr->res.cin, nr->res.n, c.groups, nr->res.taps)) ? nr->c1_frag : nc->w;
-                RUN(k.tfm(blk.tfm[ti], cur, other, L, tt, more ? blk.tfm[ti + 1].qkv_frag : nw,
-                          more ? (uint32_t)(3u * (uint32_t)c.heads * 64u * (uint32_t)C * 2u)
-                               : (nc ? (uint32_t)((size_t)nc->n * nc->taps * nc->cin_pad * 2) : 0u)));
-            }
-            RUN(k.mask(cur, L, tt, C));
+        RUN(k.mask(cur, L, tt, C));
+        block_in = cur;
+    }
+    for (size_t mi = 0; mi < h->mid.size(); ++mi) {
+        // after the last transformer block of a mid block comes the next mid block's first convolution
+        // (its fragment-order image when that ResNet block takes the three-launch path, else the row-major one)
+        const astts_flow_resnet_t* nr = mi + 1 < h->mid.size() ? &h->mid[mi + 1].res : nullptr;
+        const void* next_w = !nr ? nullptr : resnet_fused(*nr, c.groups) ? nr->c1_frag : nr->c1.w;
+        RUN(k.block(h->mid[mi], tproj_of(), cur, other, cur, L, tt, next_w, nr ? weight_bytes(nr->c1) : 0u));
+        std::swap(cur, other);
+    }
+    const float* up_src = cur;          // [b2, up_t >= skip t, C] with batch stride up_bs
+    int64_t up_bs = (int64_t)tt * C;
+    for (const astts_flow::Block& blk : h->up) {
+        --n_skips;
+        tt = skip_t[n_skips];
+        L = skip_lens[n_skips];
+        hipLaunchKernelGGL(flow_concat_skip, dim3(grid_for((int64_t)b2 * tt * 2 * (C / 4))), dim3(256), 0, st, up_src, up_bs,
+                           skips[n_skips], L, B.xin, b2, tt, C);
+        ASTTS_CHECK_LAUNCH();
+        RUN(k.block(blk, tproj_of(), B.xin, cur, other, L, tt));
+        if (blk.kind == ASTTS_FLOW_RESAMPLE_UP) {
+            // phase-decomposed ConvTranspose1d: [b2 * (tt + 1), 2C] == [b2, 2 (tt + 1), C]; output step j is row 1 + j
+            RUN(k.gemm(cur, 0, blk.resample, nullptr, B.up, 0, tt, tt + 1, 1, 1, ASTTS_ACT_NONE));
+            up_src = B.up + C;
+            up_bs = (int64_t)(tt + 1) * 2 * C;
+        } else {
+            RUN(k.gemm(cur, 0, blk.resample, nullptr, other, 0, tt, tt, 1, 1, ASTTS_ACT_NONE));
+            std::swap(cur, other);
+            up_src = cur;
+            up_bs = (int64_t)tt * C;
         }
-        const float* up_src = cur;          // [b2, up_t >= skip t, C] with batch stride up_bs
-        int64_t up_bs = (int64_t)tt * C;
-        for (size_t i = 0; i < h->up.size(); ++i) {
-            const astts_flow::Block& blk = h->up[i];
-            --n_skips;
-            tt = skip_t[n_skips];
-            L = skip_lens[n_skips];
-            hipLaunchKernelGGL(flow_concat_skip, dim3(grid_for((int64_t)b2 * tt * 2 * (C / 4))), dim3(256), 0, st, up_src, up_bs,
-                               skips[n_skips], L, B.xin, b2, tt, C);
-            ASTTS_CHECK_LAUNCH();
-            RUN(k.resnet(blk.res, tproj_of(), B.xin, L, tt, cur, blk.tfm.empty() ? nullptr : blk.tfm[0].qkv_frag, qkv_bytes));
-            for (size_t ti = 0; ti < blk.tfm.size(); ++ti) {
-                const bool more = ti + 1 < blk.tfm.size();
-                RUN(k.tfm(blk.tfm[ti], cur, other, L, tt, more ? blk.tfm[ti + 1].qkv_frag : nullptr,
-                          more ? (uint32_t)(3u * (uint32_t)c.heads * 64u * (uint32_t)C * 2u) : 0u));
-            }
-            RUN(k.mask(cur, L, tt, C));
-            if (blk.kind == ASTTS_FLOW_RESAMPLE_UP) {
-                // phase-decomposed ConvTranspose1d: [b2 * (tt + 1), 2C] == [b2, 2 (tt + 1), C]; output step j is row 1 + j
-                RUN(k.gemm(cur, 0, blk.resample, nullptr, B.up, 0, (int64_t)b2 * (tt + 1), tt, tt + 1, 1, 1, ASTTS_ACT_NONE));
-                up_src = B.up + C;
-                up_bs = (int64_t)(tt + 1) * 2 * C;
-            } else {
-                RUN(k.gemm(cur, 0, blk.resample, nullptr, other, 0, (int64_t)b2 * tt, tt, tt, 1, 1, ASTTS_ACT_NONE));
-                float* sw = cur; cur = other; other = sw;
-                up_src = cur;
-                up_bs = (int64_t)tt * C;
-            }
-        }
-        // final block at the full resolution (tt == t here: the last up block restores it)
-        float* fin = const_cast<float*>(up_src);
-        RUN(k.mask(fin, lens_full, t, C));
-        RUN(k.gemm(fin, 0, c.fin_c, nullptr, B.r1, 0, (int64_t)b2 * t, t, t, 1, 1, ASTTS_ACT_NONE));
-        RUN(k.gnorm(B.r1, lens_full, c.fin_g_w, c.fin_g_b, nullptr, B.r3, 0, t));
-        RUN(k.gemm(B.r3, 0, c.fin_p, nullptr, B.d, 0, (int64_t)b2 * t, t, t, 1, 0, ASTTS_ACT_NONE));
-        RUN(k.mask(B.d, lens_full, t, mel));
-        // x += dt * ((1 + r) d_cond - r d_uncond), every batch with its own dt and rate on its own sequences of d
-        for (int i = 0; i < k.n_seg; ++i) {
-            const Seg& g = k.seg[i];
-            RUN(astts_op_elementwise(ASTTS_EL_CFG_EULER, g.x, B.d + (size_t)g.seq0 * t * mel, nullptr, nullptr, g.x, (int64_t)g.b * t * mel, t, mel,
-                                     g.dt, g.cfg_rate, k.st));
-        }
-      }
+    }
+    // final block at the full resolution (tt == t here: the last up block restores it)
+    float* fin = const_cast<float*>(up_src);
+    RUN(k.mask(fin, lens_full, t, C));
+    RUN(k.gemm(fin, 0, c.fin_c, nullptr, B.r1, 0, t, t, 1, 1, ASTTS_ACT_NONE));
+    RUN(k.gnorm(B.r1, lens_full, c.fin_g_w, c.fin_g_b, nullptr, B.r3, 0, t));
+    RUN(k.gemm(B.r3, 0, c.fin_p, nullptr, B.d, 0, t, t, 1, 0, ASTTS_ACT_NONE));
+    RUN(k.mask(B.d, lens_full, t, mel));
+    // x += dt * ((1 + r) d_cond - r d_uncond), every batch with its own dt and rate on its own sequences of d
+    for (int i = 0; i < k.n_seg; ++i) {
+        const Seg& g = k.seg[i];
+        RUN(astts_op_elementwise(ASTTS_EL_CFG_EULER, g.x, B.d + (size_t)g.seq0 * t * mel, nullptr, nullptr, g.x, (int64_t)g.b * t * mel, t, mel,
+                                 g.dt, g.cfg_rate, k.st));
+    }
     return ASTTS_OK;
 }
 
@@ -548,6 +549,13 @@ struct FlowJoinTable {
     int n;
 };
 
+// the batch of the pass that sequence `seq` belongs to
+__device__ inline int flow_join_batch_of(const FlowJoinTable& T, int seq) {
+    int k = 0;
+    while (k + 1 < T.n && seq >= T.seq0[k] + T.b2[k]) ++k;
+    return k;
+}
+
 // tproj_out [n_res][nseq][C]: every sequence's time projection rows of its batch's CURRENT step, gathered into the contiguous block per
 // ResNet block that the kernels read; lens_full / lens_half [nseq]: the batches' lengths side by side
 __global__ __launch_bounds__(256) void flow_join_assemble(FlowJoinTable T, float* __restrict__ tproj_out, int* __restrict__ lens_full,
@@ -557,15 +565,12 @@ __global__ __launch_bounds__(256) void flow_join_assemble(FlowJoinTable T, float
         const int cc = (int)(i % C);
         const int seq = (int)((i / C) % nseq);
         const int ri = (int)(i / ((int64_t)C * nseq));
-        int k = 0;
-        while (k + 1 < T.n && seq >= T.seq0[k] + T.b2[k]) ++k;
+        const int k = flow_join_batch_of(T, seq);
         const int j = seq - T.seq0[k];
         tproj_out[i] = T.tproj[k][((int64_t)ri * T.trows[k] + (int64_t)T.step[k] * T.b2[k] + j) * C + cc];
-        if (i < nseq) {       // (i < nseq <= C * nseq: here seq == 0, so the sequence of element i is looked up again)
-            int kk = 0;
-            while (kk + 1 < T.n && (int)i >= T.seq0[kk] + T.b2[kk]) ++kk;
-            lens_full[i] = T.lens_full[kk][(int)i - T.seq0[kk]];
-            lens_half[i] = T.lens_half[kk][(int)i - T.seq0[kk]];
+        if (ri == 0 && cc == 0) {       // one element per sequence writes its lengths
+            lens_full[seq] = T.lens_full[k][j];
+            lens_half[seq] = T.lens_half[k][j];
         }
     }
 }
@@ -587,30 +592,15 @@ struct astts_flow_session {
 
 namespace {
 
-// one carve-up serves astts_flow_session_bytes (base == nullptr) and astts_flow_session_create: the buffers of a pass over the
+// one carve-up serves astts_flow_session_bytes (a counting Carver) and astts_flow_session_create: the buffers of a pass over the
 // session's maximum (carve), then every slot's time path and lengths
-size_t carve_session(const astts_flow* h, int t, int n_slots, int rows_max, int steps_max, char* base, astts_flow_session* S) {
-    const astts_flow_config_t& c = h->cfg;
-    size_t o = carve(h, rows_max, t, base, S ? &S->B : nullptr);
-    auto take = [&](size_t bytes) {
-        void* p = base ? base + o : nullptr;
-        o = align_up(o + bytes, 256);
-        return p;
-    };
-    const size_t n_res = h->down.size() + h->mid.size() + h->up.size();
-    const size_t trows = (size_t)steps_max * 2 * rows_max;
+void carve_session(Carver& cv, astts_flow_session& S, int t, int n_slots, int rows_max, int steps_max) {
+    S.B = carve(cv, S.h, rows_max, t);
     for (int i = 0; i < n_slots; ++i) {
-        astts_flow_session::Slot tmp;
-        astts_flow_session::Slot& X = S ? S->slot[i] : tmp;
-        X.T.tv = (float*)take(sizeof(float) * trows);
-        X.T.temb0 = (float*)take(sizeof(float) * trows * c.time_in);
-        X.T.temb1 = (float*)take(sizeof(float) * trows * c.time_dim);
-        X.T.temb2 = (float*)take(sizeof(float) * trows * c.time_dim);
-        X.T.tproj = (float*)take(sizeof(float) * n_res * trows * c.channels);
-        X.lens_full = (int*)take(sizeof(int) * 2 * rows_max);
-        X.lens_half = (int*)take(sizeof(int) * 2 * rows_max);
+        S.slot[i].T = carve_time(cv, S.h, steps_max, 2 * (size_t)rows_max);
+        S.slot[i].lens_full = cv.take<int>(2 * (size_t)rows_max);
+        S.slot[i].lens_half = cv.take<int>(2 * (size_t)rows_max);
     }
-    return o;
 }
 
 }  // namespace
@@ -624,33 +614,23 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
     ASTTS_REQUIRE(b >= 1 && t >= 2 && n_steps >= 1, ASTTS_ERR_INVALID, "astts_flow_solve: b=%d t=%d n_steps=%d", b, t, n_steps);
     ASTTS_REQUIRE(workspace_bytes >= astts_flow_workspace_bytes(h, b, t) && ((uintptr_t)workspace & 255) == 0,
                   ASTTS_ERR_WORKSPACE, "astts_flow_solve: workspace too small or misaligned");
-    hipStream_t st = (hipStream_t)stream;
     Seg seg{x, mu, spk, cond, 0, b, 0.0f, cfg_rate};
-    Ctx k;
-    k.h = h;
-    k.b2 = 2 * b;
-    k.T = t;
-    k.full = lens == nullptr;
-    k.st = stream;
-    k.seg = &seg;
-    k.n_seg = 1;
-    k.share = false;
-    carve(h, b, t, (char*)workspace, &k.B);
+    Carver cv{(char*)workspace, 0};
+    const Ctx k(h, carve(cv, h, b, t), t, lens == nullptr, stream, &seg, 1, false);
     const Buffers& B = k.B;
     const int b2 = k.b2, C = h->cfg.channels;
 
-    hipLaunchKernelGGL(flow_fill_lens, dim3((b2 + 63) / 64), dim3(64), 0, st, lens, B.lens_full, B.lens_half, b, t);
+    hipLaunchKernelGGL(flow_fill_lens, dim3((b2 + 63) / 64), dim3(64), 0, (hipStream_t)stream, lens, B.lens_full, B.lens_half, b, t);
     ASTTS_CHECK_LAUNCH();
 
     // the time path of all steps before the first one (time_path); solves with more than FLOW_MAX_STEPS steps evaluate it chunk by
     // chunk (the workspace holds FLOW_MAX_STEPS steps)
-    const TimeBufs T{B.tv, B.temb0, B.temb1, B.temb2, B.tproj};
     for (int s = 0; s < n_steps; ++s) {
         const int s0 = s - s % FLOW_MAX_STEPS, sl = s - s0;
         const int steps = n_steps - s0 < FLOW_MAX_STEPS ? n_steps - s0 : FLOW_MAX_STEPS;
-        if (sl == 0) RUN(time_path(k, T, t_host + s0, steps, b2));
+        if (sl == 0) RUN(time_path(k, B.T, t_host + s0, steps));
         seg.dt = dt_host[s];
-        RUN(estimator_pass(k, B.tproj + (size_t)sl * b2 * C, (size_t)steps * b2 * C, B.lens_full, B.lens_half));
+        RUN(estimator_pass(k, B.T.tproj + (size_t)sl * b2 * C, (size_t)steps * b2 * C, B.lens_full, B.lens_half));
     }
     return ASTTS_OK;
 }
@@ -658,7 +638,11 @@ int astts_flow_solve(astts_flow_t* h, float* x, const float* mu, const float* sp
 size_t astts_flow_session_bytes(const astts_flow_t* h, int32_t t, int32_t n_slots, int32_t rows_max, int32_t steps_max) {
     astts::FlowSessionPlan p;
     if (!h || p.init(t, n_slots, rows_max, steps_max) != astts::FLOW_SESSION_OK || steps_max > FLOW_MAX_STEPS) return 0;
-    return carve_session(h, t, n_slots, rows_max, steps_max, nullptr, nullptr);
+    Carver cv{nullptr, 0};
+    astts_flow_session counted;
+    counted.h = const_cast<astts_flow*>(h);
+    carve_session(cv, counted, t, n_slots, rows_max, steps_max);
+    return cv.o;
 }
 
 int astts_flow_session_create(astts_flow_t* h, int32_t t, int32_t n_slots, int32_t rows_max, int32_t steps_max, void* workspace,
@@ -674,7 +658,8 @@ int astts_flow_session_create(astts_flow_t* h, int32_t t, int32_t n_slots, int32
     s->plan = p;
     s->st = stream;
     s->passes = s->carried = 0;
-    carve_session(h, t, n_slots, rows_max, steps_max, (char*)workspace, s);
+    Carver cv{(char*)workspace, 0};
+    carve_session(cv, *s, t, n_slots, rows_max, steps_max);
     *out = s;
     return ASTTS_OK;
 }
@@ -700,17 +685,7 @@ int astts_flow_session_admit(astts_flow_session_t* s, float* x, const float* mu,
     for (int i = 0; i < n_steps; ++i) X.dt[i] = dt_host[i];
     hipLaunchKernelGGL(flow_fill_lens, dim3((2 * b + 63) / 64), dim3(64), 0, (hipStream_t)s->st, lens, X.lens_full, X.lens_half, b, t);
     ASTTS_CHECK_LAUNCH();
-    Ctx k;
-    k.h = s->h;
-    k.B = s->B;
-    k.b2 = 2 * b;
-    k.T = t;
-    k.full = X.full;
-    k.st = s->st;
-    k.seg = &X.seg;
-    k.n_seg = 1;
-    k.share = false;
-    RUN(time_path(k, X.T, t_host, n_steps, 2 * b));
+    RUN(time_path(Ctx(s->h, s->B, t, X.full, s->st, &X.seg, 1, false), X.T, t_host, n_steps));
     s->plan.admit(b, t, n_steps);
     *slot_out = slot;
     return ASTTS_OK;
@@ -730,52 +705,36 @@ int astts_flow_session_step(astts_flow_session_t* s, int32_t n_passes, uint32_t*
     for (int p = 0; p < n_passes && s->plan.n_active() > 0; ++p) {
         const int nseq = s->plan.layout();
         Seg segs[FlowSessionPlan::kSlots];
-        int of[FlowSessionPlan::kSlots];
-        int n = 0;
+        FlowJoinTable J{};
         bool full = true;
         for (int i = 0; i < s->plan.n_slots; ++i) {
             const astts::FlowSlot& ps = s->plan.s[i];
+            const astts_flow_session::Slot& X = s->slot[i];
             if (!ps.active) continue;
-            segs[n] = s->slot[i].seg;
+            const int n = J.n++;
+            segs[n] = X.seg;
             segs[n].seq0 = ps.seq0;
-            segs[n].dt = s->slot[i].dt[ps.step];
-            full = full && s->slot[i].full;
-            of[n++] = i;
+            segs[n].dt = X.dt[ps.step];
+            full = full && X.full;
+            J.tproj[n] = X.T.tproj;
+            J.lens_full[n] = X.lens_full;
+            J.lens_half[n] = X.lens_half;
+            J.seq0[n] = ps.seq0;
+            J.b2[n] = 2 * ps.b;
+            J.trows[n] = ps.n_steps * 2 * ps.b;
+            J.step[n] = ps.step;
         }
-        Ctx k;
-        k.h = s->h;
-        k.B = s->B;
-        k.b2 = nseq;
-        k.T = s->plan.t;
-        k.full = full;
-        k.st = s->st;
-        k.seg = segs;
-        k.n_seg = n;
-        k.share = share;
-        if (n == 1) {       // a lone batch: the launches of astts_flow_solve, on the batch's own tables
-            const astts_flow_session::Slot& X = s->slot[of[0]];
-            const astts::FlowSlot& ps = s->plan.s[of[0]];
-            RUN(estimator_pass(k, X.T.tproj + (size_t)ps.step * nseq * C, (size_t)ps.n_steps * nseq * C, X.lens_full, X.lens_half));
+        const Ctx k(s->h, s->B, s->plan.t, full, s->st, segs, J.n, share);
+        if (J.n == 1) {     // a lone batch: the launches of astts_flow_solve, on the batch's own tables
+            RUN(estimator_pass(k, J.tproj[0] + (size_t)J.step[0] * nseq * C, (size_t)J.trows[0] * C, J.lens_full[0], J.lens_half[0]));
         } else {
-            FlowJoinTable T{};
-            T.n = n;
-            for (int j = 0; j < n; ++j) {
-                const astts::FlowSlot& ps = s->plan.s[of[j]];
-                T.tproj[j] = s->slot[of[j]].T.tproj;
-                T.lens_full[j] = s->slot[of[j]].lens_full;
-                T.lens_half[j] = s->slot[of[j]].lens_half;
-                T.seq0[j] = ps.seq0;
-                T.b2[j] = 2 * ps.b;
-                T.trows[j] = ps.n_steps * 2 * ps.b;
-                T.step[j] = ps.step;
-            }
-            hipLaunchKernelGGL(flow_join_assemble, dim3(grid_for((int64_t)n_res * nseq * C)), dim3(256), 0, (hipStream_t)s->st, T, s->B.tproj,
+            hipLaunchKernelGGL(flow_join_assemble, dim3(grid_for((int64_t)n_res * nseq * C)), dim3(256), 0, (hipStream_t)s->st, J, s->B.T.tproj,
                                s->B.lens_full, s->B.lens_half, nseq, n_res, C);
             ASTTS_CHECK_LAUNCH();
-            RUN(estimator_pass(k, s->B.tproj, (size_t)nseq * C, s->B.lens_full, s->B.lens_half));
+            RUN(estimator_pass(k, s->B.T.tproj, (size_t)nseq * C, s->B.lens_full, s->B.lens_half));
         }
         s->passes += 1;
-        s->carried += n;
+        s->carried += J.n;
         done |= s->plan.advance();
     }
     *finished_mask_out = done;

@@ -331,3 +331,55 @@ def test_lm_workspace_bytes_layout():
                 assert int(lib.astts_lm_workspace_bytes(h, b)) == 0, (d, b)
         finally:
             lib.astts_lm_destroy(h)
+
+
+# astts_flow_workspace_bytes at (b, t) and astts_flow_session_bytes at (t, n_slots, rows_max, steps_max), as built from commit 918bc54
+FLOW_BYTES = {
+    "tiny": ((64, 2, 2, 2, 2),
+             {(1, 2): 341760, (1, 33): 727296, (1, 385): 5102592, (1, 688): 8868608,
+              (8, 2): 2728448, (8, 33): 5810688, (8, 385): 40814080, (8, 688): 70942208,
+              (32, 2): 10912256, (32, 33): 23241216, (32, 385): 163254784, (32, 688): 283767296},
+             {(33, 1, 1, 1): 737792, (344, 4, 32, 10): 159400448, (688, 2, 16, 32): 151854592}),
+    "full": ((256, 8, 2, 12, 2),
+             {(1, 2): 1755904, (1, 33): 3046144, (1, 385): 17694208, (1, 688): 30302976,
+              (8, 2): 14041600, (8, 33): 24361472, (8, 385): 141547008, (8, 688): 242417152,
+              (32, 2): 56164864, (32, 33): 97444352, (32, 385): 566186496, (32, 688): 969667072},
+             {(33, 1, 1, 1): 3098624, (344, 4, 32, 10): 577782272, (688, 2, 16, 32): 537796096}),
+}
+
+
+@pytest.mark.parametrize("name", list(FLOW_BYTES))
+def test_flow_workspace_and_session_bytes_layout(name):
+    """astts_flow_workspace_bytes and astts_flow_session_bytes are host arithmetic on the handle's config and block counts (no GPU;
+    astts_flow_create with null weight pointers copies structs only).  Callers allocate by these figures and the engine carves its
+    buffers in the same walk, so a change of any slot's size or order shows here: the values are recorded from commit 918bc54."""
+    from astts import _lib_session, ops
+
+    lib = _lib_session.load()
+    (ch, heads, n_down, n_mid, n_up), solve_bytes, session_bytes = FLOW_BYTES[name]
+    cfg = ops.FlowConfig(mel=80, channels=ch, heads=heads, groups=8, time_in=320, time_dim=4 * ch, n_down=n_down, n_mid=n_mid, n_up=n_up)
+
+    def blocks(kinds):
+        arr = (ops.FlowBlock * len(kinds))()
+        for blk, kind in zip(arr, kinds):
+            blk.resample_kind = kind
+        return arr
+
+    down = blocks([ops.FLOW_RESAMPLE_DOWN] * (n_down - 1) + [ops.FLOW_RESAMPLE_CONV])
+    mid = blocks([ops.FLOW_RESAMPLE_NONE] * n_mid)
+    up = blocks([ops.FLOW_RESAMPLE_UP] * (n_up - 1) + [ops.FLOW_RESAMPLE_CONV])
+    h = ctypes.c_void_p()
+    assert lib.astts_flow_create(ctypes.byref(cfg), down, mid, up, ctypes.byref(h)) == 0 and h.value
+    try:
+        for (b, t), want in solve_bytes.items():
+            assert int(lib.astts_flow_workspace_bytes(h, b, t)) == want, (b, t)
+        for args, want in session_bytes.items():
+            assert int(lib.astts_flow_session_bytes(h, *args)) == want, args
+        for b, t in ((0, 33), (-1, 33), (8, 0), (8, -1)):
+            assert int(lib.astts_flow_workspace_bytes(h, b, t)) == 0, (b, t)
+        assert int(lib.astts_flow_workspace_bytes(None, 8, 33)) == 0
+        assert int(lib.astts_flow_session_bytes(None, 344, 4, 32, 10)) == 0
+        assert int(lib.astts_flow_session_bytes(h, 344, 4, 32, 33)) == 0          # steps_max > 32
+        assert int(lib.astts_flow_session_bytes(h, 344, 5, 32, 10)) == 0          # n_slots > 4
+    finally:
+        lib.astts_flow_destroy(h)

@@ -126,6 +126,7 @@ def full_flow():
     (64, (5, 4), (0, 1)),                   # 18 sequences against 10 and 8 alone: crosses tfm_attn_fused's switch at 2 * heads * b > 256
     (96, (8, 8, 8, 8), (0, 0, 1, 2)),       # 64 sequences x 3 tiles = 192 tiles against 48 alone: the ordinary rconv_lds form both ways
     (225, (8, 8, 8, 8), (0, 1, 1, 2)),      # 64 sequences x 8 tiles = 512 tiles: rconv_lds's SHARE form joined, the ordinary one alone
+    (385, (1, 2), (0, 2)),                  # unfused attention (t > 384); the batch joins at the first one's last step
 ])
 def test_fullsize_batches_join_a_running_solve_bit_identical(full_flow, t, rows, joins):
     cfg, fd = full_flow

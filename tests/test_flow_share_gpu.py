@@ -232,6 +232,7 @@ ENGINE_CASES = [
     (64, (5, 4), (0, 1)),                   # 20 and 16 feed-forward tiles
     (97, (5, 3, 8), (0, 1, 1)),             # odd length, partial tiles, unequal batches whose GEMM plans may differ
     (96, (8, 8, 8, 8), (0, 0, 1, 2)),
+    (385, (2, 1), (0, 1)),                  # past the fused attention's 384 frames: the q|k|v GEMM of the unfused branch is grouped by plan
 ]
 
 

@@ -396,11 +396,12 @@ def test_ragged_vocoder_batch_equals_one_at_a_time(wide):
 
 
 @pytest.mark.parametrize("b,t,ragged,wide", [(2, 57, False, False), (3, 64, True, False), (1, 33, True, False), (2, 70, True, True),
-                                             (2, 64, False, True)])
+                                             (2, 64, False, True), (1, 385, False, True), (2, 386, True, True)])
 def test_flow_solver_engine_is_bit_identical_to_operator_path(b, t, ragged, wide):
     """astts_flow_solve (C++ host loop) issues the same kernels as the operator-by-operator Python solve:
     the solved mel must be identical bit for bit (odd and even T exercise the stride-2 level and its transposed
-    convolution; ragged rows exercise every length mask)."""
+    convolution; ragged rows exercise every length mask).  T = 385 / 386 at 256 channels: the first frame counts past the fused
+    attention's limit of 384, so LayerNorm + q|k|v GEMM + flash attention run in front of the fused feed-forward."""
     from astts.synth.model import FlowDecoder
 
     cfg, W = _cfg_and_weights()
