@@ -24,6 +24,10 @@ return the inner product (descending) / the squared Euclidean distance (ascendin
 expressions over the primary key and the dynamic fields (astts.milvus_filter) become a row mask of the search kernels;
 ``limit`` up to 1024 (32 hits per selection pass over one scan).
 
+``MilvusClient(uri, use_index=True)`` honours ``create_index(... "IVF_FLAT", {"nlist": N})`` and ``param={"nprobe": P}``
+(include/knn/astts_knn_ivf.h: k-means lists, the exact answer over the rows of the P closest lists).  Without the keyword -- the
+default -- an index request only records its parameters, ``nprobe`` is ignored and every search is the exact brute-force one.
+
 The file behind ``db_path`` is read with astts.milvus_lite (SQLite + protobuf wire format); the
 vectors go to HBM once per collection and stay there: ``insert`` appends to the resident bank, ``delete`` / ``upsert`` tombstone its
 rows, ``compact`` squeezes them out (astts.knn.StyleBank.append / delete_rows / compact).  Errors raise ``MilvusException`` -- the
@@ -99,6 +103,8 @@ class _Collection:
         self.live: List[bool] = []      # vectors / pks / metas / live are row-aligned with the bank; a deleted row stays until compact
         self.n_live = 0
         self._bank = None  # astts.knn.StyleBank, built lazily by the first search, then kept up to date in place
+        self.use_index = False      # MilvusClient(use_index=True): an IVF_FLAT index request is built on the resident bank
+        self._index_nlist: Optional[int] = None      # the nlist the bank's index was built for
         self._group_codes: Dict[str, Any] = {}      # group_by_field -> (int32 codes [rows], groups); dropped whenever the rows change
 
     def group_codes(self, field: str):
@@ -125,6 +131,45 @@ class _Collection:
             codes[i] = seen.setdefault(key, len(seen))
         self._group_codes[field] = (codes, max(len(seen), 1))
         return self._group_codes[field]
+
+    def ivf_nlist(self) -> Optional[int]:
+        """``nlist`` of the recorded index request when its type is IVF_FLAT (default 128, Milvus' own), else None.  The request is
+        kept as strings (create_index; the Milvus-Lite file): ``nlist`` flat or inside the ``params`` dictionary."""
+        if str(self.index_params.get("index_type", "")).upper() != "IVF_FLAT":
+            return None
+        nlist = self.index_params.get("nlist")
+        if nlist is None:
+            inner = self.index_params.get("params")
+            if isinstance(inner, str):
+                import ast
+                try:
+                    inner = ast.literal_eval(inner)
+                except (ValueError, SyntaxError):
+                    inner = None
+            if isinstance(inner, dict):
+                nlist = inner.get("nlist")
+        try:
+            nlist = int(nlist) if nlist is not None else 128
+        except (TypeError, ValueError):
+            raise MilvusException(1100, f"invalid nlist {nlist!r} of the IVF_FLAT index of {self.name}") from None
+        if nlist < 1:
+            raise MilvusException(1100, f"invalid nlist {nlist} of the IVF_FLAT index of {self.name}")
+        return nlist
+
+    def sync_index(self) -> None:
+        """The resident bank's index as the recorded request and ``use_index`` want it: built (trained once, when the bank goes
+        resident or the request arrives; inserts, deletes and compaction keep it in step through StyleBank), or absent."""
+        if self._bank is None or self._bank.live == 0:      # (an index needs a live row: built by the first search after an insert)
+            return
+        nlist = self.ivf_nlist() if self.use_index else None
+        have = self._bank.index_info()
+        if nlist is None:
+            if have is not None:
+                self._bank.drop_index()
+        elif have is None or self._index_nlist != nlist:
+            self._bank.build_index(nlist)
+            self._index_nlist = nlist
+
     def live_rows(self) -> List[int]:
         return [i for i, on in enumerate(self.live) if on]
 
@@ -143,14 +188,22 @@ class _Collection:
             self._bank = StyleBank(m16 if np.array_equal(m16.astype(np.float32), m) else m, metric=self.metric)
             if self.n_live < len(self.live):      # rows deleted before the first search: the bank stays row-aligned with the lists
                 self._bank.delete_rows([i for i, on in enumerate(self.live) if not on])
+            self._index_nlist = None
+            self.sync_index()
         return self._bank
 
 
 class MilvusClient:
-    def __init__(self, uri: str = "./milvus_demo.db", persist: bool = True, **_kwargs):
+    def __init__(self, uri: str = "./milvus_demo.db", persist: bool = True, use_index: bool = False, **_kwargs):
         """``uri`` is a Milvus-Lite file path, loaded if it exists.  As with pymilvus, create_collection / insert /
-        drop_collection are written through to that file (created on first write) unless ``persist=False``."""
+        drop_collection are written through to that file (created on first write) unless ``persist=False``.
+
+        ``use_index``: a collection whose recorded index type is IVF_FLAT gets that index (its ``nlist``) when its bank goes
+        resident, and ``search`` probes ``nprobe`` lists (``param`` / ``search_params``; 8 when absent).  FLAT / AUTOINDEX / no
+        index, grouped and ranged searches: brute force.  Centroids are not stored in the file: training is deterministic, a
+        reload rebuilds the same index.  Off by default: ``nprobe`` is then ignored and every search is exact."""
         self.uri = uri
+        self._use_index = bool(use_index)
         self._persist = bool(persist) and "://" not in uri
         self._writer: Optional[MilvusLiteWriter] = None
         self._colls: Dict[str, _Collection] = {}
@@ -168,6 +221,7 @@ class MilvusClient:
                     c.metas = metas
                     c.live = [True] * len(c.pks)
                     c.n_live = len(c.pks)
+                    c.use_index = self._use_index
                     self._colls[name] = c
             finally:
                 f.close()
@@ -225,19 +279,26 @@ class MilvusClient:
         self._colls[collection_name] = _Collection(collection_name, int(dimension), metric_type,
                                                    primary_field_name, vector_field_name)
         self._colls[collection_name].auto_id = auto_id
+        self._colls[collection_name].use_index = self._use_index
         if self._file():
             self._file().create_collection(collection_name, int(dimension), metric_type, primary_field_name,
                                            vector_field_name)
 
     def create_index(self, collection_name: str, field_name: Optional[str] = None, index_params=None, **_kw) -> None:
-        """milvus/insert_embeddings.py:75-79.  The search here is exact brute force on the GPU, so an index request only
-        records its parameters (and a metric, if it names one, for a collection that has no rows yet)."""
+        """milvus/insert_embeddings.py:75-79.  By default the search here is exact brute force on the GPU, so an index request only
+        records its parameters (and a metric, if it names one, for a collection that has no rows yet).  A client made with
+        ``use_index=True`` builds an IVF_FLAT request on the resident bank (at once when the bank is resident, else when it goes)."""
         c = self._get(collection_name)
         params = dict(index_params) if isinstance(index_params, dict) else {}
         mt = params.get("metric_type") or (params.get("params") or {}).get("metric_type")
         if mt and not c.pks:
             c.metric = str(mt).upper()
         c.index_params.update({k: str(v) for k, v in params.items()})
+        if self._use_index:
+            if "nlist" in c.index_params and "nlist" not in params:      # (an earlier request's: this one names its own, or none)
+                del c.index_params["nlist"]
+            c.ivf_nlist()           # a bad nlist is refused here, not at the first search
+            c.sync_index()
 
     def drop_collection(self, collection_name: str, **_kw) -> None:
         if self._colls.pop(collection_name, None) is not None and self._file():
@@ -405,6 +466,22 @@ class MilvusClient:
         return self.hits_from_rows(collection_name, idx, score, output_fields, group_by_field=group_by_field)
 
     @staticmethod
+    def _nprobe_of(search_params: Optional[dict], param: Optional[dict]) -> int:
+        """``nprobe`` of a request: from param["params"], search_params["params"], flat ``param`` (the reference:
+        ``param={"nprobe": 10}``) or flat ``search_params``; 8 when absent.  Below 1 is refused."""
+        for src in ((param or {}).get("params"), (search_params or {}).get("params"), param, search_params):
+            if isinstance(src, dict) and src.get("nprobe") is not None:
+                try:
+                    nprobe = int(src["nprobe"])
+                except (TypeError, ValueError):
+                    raise MilvusException(1100, f"invalid nprobe {src['nprobe']!r}") from None
+                if nprobe < 1:
+                    raise MilvusException(1100, f"nprobe {nprobe} is invalid: it must be at least 1")
+                return nprobe
+        from .._lib_knn_ivf import DEFAULT_NPROBE
+        return DEFAULT_NPROBE
+
+    @staticmethod
     def _range_of(metric: str, search_params: Optional[dict], param: Optional[dict]):
         """(radius, range_filter) of a request, None where absent: from search_params["params"], param["params"], flat search_params."""
         out = []
@@ -488,6 +565,16 @@ class MilvusClient:
             # milvus/search_embeddings.py:64).  Here: 32 certified hits per selection pass, at most 32 passes.
             raise MilvusException(1100, f"limit {limit} is not supported by this build: at most {KNN_MAX_K} hits per query "
                                         f"(collection holds {c.n_live} rows)")
+        if self._use_index and c.ivf_nlist() is not None:      # (grouped and ranged searches stay on the brute-force path above)
+            nprobe = self._nprobe_of(search_params, param)
+            bank = c.bank()
+            c.sync_index()
+            from .._lib import AsttsError
+            try:
+                idx, score = bank.search_ivf(q, k, nprobe, row_mask=mask)
+            except AsttsError as e:      # (more than 1024 lists to probe: refused, never answered by another search)
+                raise MilvusException(1100, f"IVF_FLAT search refused: {e}") from None
+            return np.asarray(idx, dtype=np.int64), np.asarray(score, dtype=np.float32)
         idx, score = c.bank().search(q, k, row_mask=mask) if mask is not None else c.bank().search(q, k)
         return np.asarray(idx, dtype=np.int64), np.asarray(score, dtype=np.float32)
 

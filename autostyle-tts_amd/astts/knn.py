@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, _lib_knn, _lib_knn_grouped
+from . import _lib, _lib_knn, _lib_knn_grouped, _lib_knn_ivf
 
 
 KNN_SCANS = ("DIRECT", "REGISTER", "GEMM", "GEMM_BLOCKS", "GEMM_N_FIRST")      # ASTTS_KNN_SCAN_*
@@ -59,6 +59,11 @@ class StyleBank:
     tombstones rows (no search returns them; row indices stay), ``compact`` squeezes the tombstones out and renumbers.  ``n`` rows,
     ``live`` of them not deleted, ``capacity`` rows allocated.  None of these may run while a search of this bank is in flight on
     another stream or thread.
+
+    ``build_index`` adds an IVF_FLAT index (include/knn/astts_knn_ivf.h): ``search_ivf`` / ``search_ivf_device`` then return the exact
+    answer over the rows of the ``nprobe`` lists closest to each query.  ``search`` / ``search_device`` stay the brute-force search.
+    With an index present ``append`` assigns the new rows to their lists and ``compact`` renumbers the lists; ``delete_rows`` needs
+    nothing (the list scan skips tombstones).
     """
 
     def __init__(self, vectors, device: Optional[torch.device] = None, metric: str = "COSINE"):
@@ -94,6 +99,9 @@ class StyleBank:
         self._gws: Optional[torch.Tensor] = None     # the grouped search's workspace and its plans per (nq, limit, group_size, n_groups)
         self._gplans: dict = {}
         self.last_rounds = 0                         # rounds the last grouped search took (rounds_host)
+        self._ivf = None                             # astts_knn_ivf_t* (build_index), its workspace and its plans per (nq, k, nprobe)
+        self._iws: Optional[torch.Tensor] = None
+        self._iplans: dict = {}
         self._search = lib.astts_knn_search
         self._refresh()
 
@@ -106,6 +114,7 @@ class StyleBank:
         self.scan_plane_exact = bool(exact.value)
         self._plans = {}
         self._gplans = {}
+        self._iplans = {}
 
     # ---- mutation (each call synchronises the current stream, as the constructor does)
     def reserve(self, capacity: int) -> None:
@@ -136,6 +145,8 @@ class StyleBank:
                                                             _lib.stream_ptr(), ctypes.byref(first)))
             finally:
                 self._refresh()
+            if self._ivf is not None:
+                _lib.check(_lib_knn_ivf.load().astts_knn_ivf_assign(self._ivf, self._h, _lib.stream_ptr()))
         return int(first.value)
 
     def delete_rows(self, rows) -> None:
@@ -157,9 +168,13 @@ class StyleBank:
                 _lib.check(_lib_knn.load().astts_knn_compact(self._h, _lib.stream_ptr(), None, old_to_new.ctypes.data))
             finally:
                 self._refresh()
+            if self._ivf is not None:
+                _lib.check(_lib_knn_ivf.load().astts_knn_ivf_remap(self._ivf, old_to_new.ctypes.data, self.n, _lib.stream_ptr()))
         return old_to_new
 
     def close(self) -> None:
+        if getattr(self, "_ivf", None):
+            self.drop_index()
         if getattr(self, "_h", None):
             _lib.load().astts_knn_destroy(self._h)
             self._h = None
@@ -345,6 +360,123 @@ class StyleBank:
         idx, sc = self.search_grouped_device(q.to(self.device), limit, group_size, groups, n_groups, radius, range_filter, row_mask,
                                              force_exact, max_rounds=max_rounds)
         return idx.cpu().numpy(), sc.cpu().numpy()
+
+    # ---- IVF_FLAT index (include/knn/astts_knn_ivf.h)
+    def build_index(self, nlist: int, niter: int = _lib_knn_ivf.DEFAULT_NITER, centroids=None) -> dict:
+        """Train ``min(nlist, live rows)`` k-means lists over the bank (``niter`` Lloyd iterations from ``centroids`` -- numpy / torch
+        fp32 ``[nlist, D]`` -- or, when None, from evenly spaced live rows) and assign every row to its closest centroid; replaces an
+        index the bank has.  Deterministic: the same bank and arguments give byte-identical centroids and lists.  ``niter=0`` with
+        given centroids is a pure assignment.  Synchronises the current stream.  -> ``index_info()``."""
+        nlist, niter = int(nlist), int(niter)
+        if not 1 <= nlist <= _lib_knn_ivf.MAX_NLIST or niter < 0:
+            raise ValueError(f"nlist must be in 1..{_lib_knn_ivf.MAX_NLIST} and niter >= 0, got nlist={nlist} niter={niter}")
+        cptr = None
+        if centroids is not None:
+            c = centroids.detach().cpu().numpy() if isinstance(centroids, torch.Tensor) else np.asarray(centroids)
+            c = np.ascontiguousarray(c, dtype=np.float32)
+            if c.shape != (nlist, self.d):
+                raise ValueError(f"centroids must be [{nlist}, {self.d}], got {tuple(c.shape)}")
+            cptr = c.ctypes.data
+        self.drop_index()
+        ivf = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib_knn_ivf.load().astts_knn_ivf_create(self._h, nlist, niter, cptr, _lib.stream_ptr(), ctypes.byref(ivf)))
+        self._ivf = ivf
+        return self.index_info()
+
+    def drop_index(self) -> None:
+        if self._ivf is not None:
+            _lib_knn_ivf.load().astts_knn_ivf_destroy(self._ivf)
+            self._ivf = None
+        self._iplans = {}
+
+    def index_info(self) -> Optional[dict]:
+        """None without an index, else ``{"index_type": "IVF_FLAT", "nlist", "n_indexed", "max_list_len"}`` (``nlist``: the lists that
+        exist, ``min`` of the request and the live rows at build time; ``max_list_len`` counts tombstoned rows)."""
+        if self._ivf is None:
+            return None
+        nl, ni, ml = ctypes.c_int32(), ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib_knn_ivf.load().astts_knn_ivf_info(self._ivf, ctypes.byref(nl), ctypes.byref(ni), ctypes.byref(ml)))
+        return {"index_type": "IVF_FLAT", "nlist": int(nl.value), "n_indexed": int(ni.value), "max_list_len": int(ml.value)}
+
+    def index_export(self):
+        """-> (centroids fp32 ``[nlist, D]``, list_of int32 ``[n]``) as numpy arrays (synchronises)."""
+        info = self.index_info()
+        if info is None:
+            raise RuntimeError("the bank has no index: build_index first")
+        cent = np.empty((info["nlist"], self.d), np.float32)
+        list_of = np.empty(info["n_indexed"], np.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib_knn_ivf.load().astts_knn_ivf_export(self._ivf, cent.ctypes.data, list_of.ctypes.data))
+        return cent, list_of
+
+    def search_ivf_device(self, queries: torch.Tensor, k: int, nprobe: int = _lib_knn_ivf.DEFAULT_NPROBE,
+                          row_mask: Optional[torch.Tensor] = None, return_f64: bool = False):
+        """``search_device`` over the rows of the ``min(nprobe, nlist)`` lists whose centroids are closest to each query: the same
+        order, and for every hit bit for bit the scores ``search_device`` returns for it; -1 / -inf (+inf for L2) where the probed
+        lists hold fewer than ``k`` allowed rows.  ``nprobe >= nlist`` is the brute-force result.  Enqueued on the current stream,
+        no synchronisation."""
+        if self._ivf is None:
+            raise RuntimeError("the bank has no index: build_index first (there is no quiet fall-back to the brute-force search)")
+        if queries.dim() != 2 or queries.shape[1] != self.d:
+            raise ValueError(f"queries must be [Q, {self.d}], got {tuple(queries.shape)}")
+        k, nprobe = int(k), int(nprobe)
+        if not 1 <= k <= _lib.KNN_MAX_K:
+            raise ValueError(f"k must be in 1..{_lib.KNN_MAX_K}, got {k}")
+        if nprobe < 1:
+            raise ValueError(f"nprobe must be >= 1, got {nprobe}")
+        q = queries
+        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
+            q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        nq = int(q.shape[0])
+        out_idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        out_score = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        s64 = torch.empty((nq, k), dtype=torch.float64, device=self.device) if return_f64 else None
+        if nq == 0:
+            return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+        lib = _lib_knn_ivf.load()
+        with torch.cuda.device(self.device):
+            key = (nq, k, nprobe)
+            plan = self._iplans.get(key)
+            if plan is None:
+                need = int(lib.astts_knn_ivf_workspace_bytes(self._ivf, self._h, nq, k, nprobe))
+                if need == 0:
+                    raise ValueError(f"invalid IVF search shape nq={nq} k={k} nprobe={nprobe}")
+                if self._iws is None or self._iws.numel() < need + 256:
+                    self._iws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                    self._iplans = {}
+                base = self._iws.data_ptr()
+                aligned = (base + 255) // 256 * 256
+                plan = self._iplans[key] = (self._iws, aligned, self._iws.numel() - (aligned - base))
+            _, aligned, ws_bytes = plan
+            mptr, mstride = None, 0
+            if row_mask is not None:
+                m = row_mask.to(device=self.device)
+                m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
+                if m.shape == (self.n,):
+                    mstride = 0
+                elif m.shape == (nq, self.n):
+                    mstride = self.n
+                else:
+                    raise ValueError(f"row_mask must be [{self.n}] or [{nq}, {self.n}], got {tuple(m.shape)}")
+                mptr = m.data_ptr()
+            rc = lib.astts_knn_ivf_search(self._ivf, self._h, q.data_ptr(), nq, k, nprobe, out_idx.data_ptr(), out_score.data_ptr(),
+                                          None if s64 is None else s64.data_ptr(), mptr, mstride, aligned, ws_bytes,
+                                          torch.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                _lib.check(rc)
+        return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+
+    def search_ivf(self, queries, k: int, nprobe: int = _lib_knn_ivf.DEFAULT_NPROBE, row_mask=None, return_f64: bool = False):
+        """Host convenience of ``search_ivf_device``: accepts numpy / lists, returns numpy (idx int64 [Q,k], score fp32 [Q,k] and,
+        with ``return_f64``, score fp64 [Q,k])."""
+        q = torch.as_tensor(np.asarray(queries, dtype=np.float32))
+        if q.dim() == 1:
+            q = q[None, :]
+        if row_mask is not None and not isinstance(row_mask, torch.Tensor):
+            row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
+        out = self.search_ivf_device(q.to(self.device), k, nprobe, row_mask=row_mask, return_f64=return_f64)
+        return tuple(t.cpu().numpy() for t in out)
 
     def route(self, nq: int, k: int, masked: bool = False, aligned: bool = True):
         """``route`` (above) for a search of this bank: ``[(rows, scan, finish), ...]``, one per query group.  A bank with tombstones
