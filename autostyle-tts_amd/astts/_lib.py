@@ -88,38 +88,58 @@ def parse_prototypes(text: str) -> dict:
     return sigs
 
 
+def _header_signatures(paths, what: str) -> dict:
+    sigs = {}
+    for path in paths:
+        if not os.path.exists(path):
+            raise AsttsLibraryMissing(f"{path} not found: the ctypes signatures of {what} are derived from this header")
+        with open(path) as f:
+            sigs.update(parse_prototypes(f.read()))
+    return sigs
+
+
+def _set_prototypes(lib, sigs: dict):
+    for name, (res, args) in sigs.items():
+        fn = getattr(lib, name)  # AttributeError if the .so does not export it
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 @functools.lru_cache(maxsize=None)
 def signatures() -> dict:
     """The C ABI as include/astts.h declares it: the header is the one place where a signature is written.  Parsed once."""
-    if not os.path.exists(HEADER_PATH):
-        raise AsttsLibraryMissing(f"{HEADER_PATH} not found: the ctypes signatures of libastts.so are derived from this header")
-    with open(HEADER_PATH) as f:
-        return parse_prototypes(f.read())
+    return _header_signatures((HEADER_PATH,), "libastts.so")
 
 
 def declared_symbols():
     return sorted(signatures())
 
 
-_lib = None
-
-
+@functools.lru_cache(maxsize=None)
 def load():
     """Load libastts.so (once).  Raises AsttsLibraryMissing when it has not been built."""
-    global _lib
-    if _lib is not None:
-        return _lib
     if not os.path.exists(LIB_PATH):
         raise AsttsLibraryMissing(
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"or `make -C autostyle-tts_amd/csrc`.  There is no CPU fallback.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in signatures().items():
-        fn = getattr(lib, name)  # AttributeError if the .so does not export it
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    return _set_prototypes(ctypes.CDLL(LIB_PATH), signatures())
+
+
+def bind_headers(*paths: str, what: str):
+    """The binding of headers beside include/astts.h whose calls libastts.so exports too (include/knn/, include/llm/,
+    include/session/): -> (signatures, load).  ``signatures()``: name -> (restype, argtypes) of every prototype of ``paths``, parsed
+    once; ``load()``: the library object of ``load`` above with those prototypes set, once.  ``what`` names the calls in the message
+    of a missing header."""
+    @functools.lru_cache(maxsize=None)
+    def header_signatures() -> dict:
+        return _header_signatures(paths, what)
+
+    @functools.lru_cache(maxsize=None)
+    def load_bound():
+        return _set_prototypes(load(), header_signatures())
+
+    return header_signatures, load_bound
 
 
 def check(code: int) -> None:

@@ -1,11 +1,10 @@
 """ctypes binding of the mutable style-bank entry points of libastts.so (include/knn/astts_knn_mutable.h).
 
 The calls live in libastts.so itself; their signatures are parsed from their own header exactly as astts/_lib.py parses
-include/astts.h, and set on the library object that module loads.
+include/astts.h, and set on the library object that module loads (astts._lib.bind_headers).
 """
 from __future__ import annotations
 
-import functools
 import os
 
 from . import _lib
@@ -13,21 +12,4 @@ from . import _lib
 HEADER_PATH = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "include", "knn",
                                             "astts_knn_mutable.h"))
 
-
-@functools.lru_cache(maxsize=None)
-def signatures() -> dict:
-    if not os.path.exists(HEADER_PATH):
-        raise _lib.AsttsLibraryMissing(f"{HEADER_PATH} not found: the ctypes signatures of the style-bank mutations are derived from this header")
-    with open(HEADER_PATH) as f:
-        return _lib.parse_prototypes(f.read())
-
-
-@functools.lru_cache(maxsize=None)
-def load():
-    """libastts.so with the prototypes of the style-bank mutations set (once)."""
-    lib = _lib.load()
-    for name, (res, args) in signatures().items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    return lib
+signatures, load = _lib.bind_headers(HEADER_PATH, what="the style-bank mutations")

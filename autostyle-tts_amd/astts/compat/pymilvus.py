@@ -368,12 +368,17 @@ class MilvusClient:
             want = {int(i) for i in ([ids] if isinstance(ids, (int, np.integer)) else ids)}
             keep &= np.fromiter((pk in want for pk in c.pks), dtype=bool, count=len(c.pks))
         if filter:
-            from ..milvus_filter import FilterSyntaxError, row_mask
-            try:
-                keep &= row_mask(filter, c.pk_field, c.pks, c.metas).astype(bool)
-            except FilterSyntaxError as e:
-                raise MilvusException(1100, f"failed to create query plan: cannot parse expression: {filter}, error: {e}") from None
+            keep &= self._filter_mask(c, filter).astype(bool)
         return [int(i) for i in np.flatnonzero(keep)]
+
+    @staticmethod
+    def _filter_mask(c: _Collection, filter: str) -> np.ndarray:
+        """``filter`` compiled to a mask over the rows of ``c`` (astts.milvus_filter), non-zero where a row satisfies it."""
+        from ..milvus_filter import FilterSyntaxError, row_mask
+        try:
+            return row_mask(filter, c.pk_field, c.pks, c.metas)
+        except FilterSyntaxError as e:
+            raise MilvusException(1100, f"failed to create query plan: cannot parse expression: {filter}, error: {e}") from None
 
     def delete(self, collection_name: str, ids=None, filter: Optional[str] = None, **_kw) -> Dict[str, Any]:
         """Exactly one of ``ids`` (one primary key or a list) / ``filter``.  -> ``{"delete_count": rows deleted}``: every live row
@@ -466,33 +471,36 @@ class MilvusClient:
         return self.hits_from_rows(collection_name, idx, score, output_fields, group_by_field=group_by_field)
 
     @staticmethod
+    def _request_param(name: str, sources):
+        """``name`` of a request: its value in the first of ``sources`` -- dictionaries, or None where the request has none, in the
+        order of their precedence -- that holds one; None when absent."""
+        for src in sources:
+            if isinstance(src, dict) and src.get(name) is not None:
+                return src[name]
+        return None
+
+    @staticmethod
     def _nprobe_of(search_params: Optional[dict], param: Optional[dict]) -> int:
         """``nprobe`` of a request: from param["params"], search_params["params"], flat ``param`` (the reference:
         ``param={"nprobe": 10}``) or flat ``search_params``; 8 when absent.  Below 1 is refused."""
-        for src in ((param or {}).get("params"), (search_params or {}).get("params"), param, search_params):
-            if isinstance(src, dict) and src.get("nprobe") is not None:
-                try:
-                    nprobe = int(src["nprobe"])
-                except (TypeError, ValueError):
-                    raise MilvusException(1100, f"invalid nprobe {src['nprobe']!r}") from None
-                if nprobe < 1:
-                    raise MilvusException(1100, f"nprobe {nprobe} is invalid: it must be at least 1")
-                return nprobe
-        from .._lib_knn_ivf import DEFAULT_NPROBE
-        return DEFAULT_NPROBE
+        given = MilvusClient._request_param("nprobe", ((param or {}).get("params"), (search_params or {}).get("params"), param, search_params))
+        if given is None:
+            from .._lib_knn_ivf import DEFAULT_NPROBE
+            return DEFAULT_NPROBE
+        try:
+            nprobe = int(given)
+        except (TypeError, ValueError):
+            raise MilvusException(1100, f"invalid nprobe {given!r}") from None
+        if nprobe < 1:
+            raise MilvusException(1100, f"nprobe {nprobe} is invalid: it must be at least 1")
+        return nprobe
 
     @staticmethod
     def _range_of(metric: str, search_params: Optional[dict], param: Optional[dict]):
         """(radius, range_filter) of a request, None where absent: from search_params["params"], param["params"], flat search_params."""
-        out = []
-        for name in ("radius", "range_filter"):
-            v = None
-            for src in ((search_params or {}).get("params"), (param or {}).get("params"), search_params):
-                if isinstance(src, dict) and src.get(name) is not None:
-                    v = float(src[name])
-                    break
-            out.append(v)
-        radius, range_filter = out
+        sources = ((search_params or {}).get("params"), (param or {}).get("params"), search_params)
+        radius, range_filter = (None if v is None else float(v)
+                                for v in (MilvusClient._request_param(name, sources) for name in ("radius", "range_filter")))
         if radius is not None and range_filter is not None and (range_filter >= radius if metric == "L2" else radius >= range_filter):
             raise MilvusException(1100, f"range_filter({range_filter}) must be "
                                         f"{'less' if metric == 'L2' else 'greater'} than radius({radius}) for {metric}")
@@ -521,13 +529,7 @@ class MilvusClient:
             raise MilvusException(1100, f"offset {offset} / group_size {group_size} is invalid")
         groups = c.group_codes(group_by_field) if group_by_field else None
         selecting = groups is not None or int(offset) > 0 or radius is not None or range_filter is not None
-        mask = None
-        if filter:          # (the reference passes None: milvus/search_json.py:246-252)
-            from ..milvus_filter import FilterSyntaxError, row_mask
-            try:
-                mask = row_mask(filter, c.pk_field, c.pks, c.metas)
-            except FilterSyntaxError as e:
-                raise MilvusException(1100, f"failed to create query plan: cannot parse expression: {filter}, error: {e}") from None
+        mask = self._filter_mask(c, filter) if filter else None      # (the reference passes None: milvus/search_json.py:246-252)
         if anns_field is not None and anns_field != c.vector_field:
             raise MilvusException(1, f"anns_field {anns_field!r} does not exist (vector field is {c.vector_field!r})")
         mt = metric_type or (search_params or {}).get("metric_type") or (param or {}).get("metric_type")
@@ -543,7 +545,8 @@ class MilvusClient:
             return np.zeros((q.shape[0], 0), np.int64), np.zeros((q.shape[0], 0), np.float32)
         if limit < 1:
             raise MilvusException(1, f"limit {limit} is invalid")
-        from .._lib import KNN_MAX_K
+        from .._lib import KNN_MAX_K, AsttsError
+        skip = 0            # columns sliced away behind the search
         if selecting:       # limit + offset groups (hits) of group_size rows, sliced behind the search
             gs = min(int(group_size), c.n_live) if groups is not None else 1
             want = min(int(limit) + int(offset), c.n_live)
@@ -551,32 +554,32 @@ class MilvusClient:
                 raise MilvusException(1100, f"limit {limit} (+ offset {offset}, x group_size {gs}) is not supported by this build: at most "
                                             f"{KNN_MAX_K} hits per query (collection holds {c.n_live} rows)")
             codes, n_groups = groups if groups is not None else (None, None)
-            from .._lib import AsttsError
-            try:
-                idx, score = c.bank().search_grouped(q, want, gs, groups=codes, n_groups=n_groups, radius=radius,
-                                                     range_filter=range_filter, row_mask=mask)
-            except AsttsError as e:      # (the rounds ran out: never a partial answer)
-                raise MilvusException(1100, f"grouped search refused: {e}") from None
             skip = min(int(offset), want) * gs
-            return np.asarray(idx, dtype=np.int64)[:, skip:], np.asarray(score, dtype=np.float32)[:, skip:]
-        k = min(int(limit), c.n_live)
-        if k > KNN_MAX_K:
-            # pymilvus accepts limit up to 16384; the reference asks for 1 or 3 (milvus/search_json.py:411,
-            # milvus/search_embeddings.py:64).  Here: 32 certified hits per selection pass, at most 32 passes.
-            raise MilvusException(1100, f"limit {limit} is not supported by this build: at most {KNN_MAX_K} hits per query "
-                                        f"(collection holds {c.n_live} rows)")
-        if self._use_index and c.ivf_nlist() is not None:      # (grouped and ranged searches stay on the brute-force path above)
-            nprobe = self._nprobe_of(search_params, param)
-            bank = c.bank()
-            c.sync_index()
-            from .._lib import AsttsError
-            try:
-                idx, score = bank.search_ivf(q, k, nprobe, row_mask=mask)
-            except AsttsError as e:      # (more than 1024 lists to probe: refused, never answered by another search)
-                raise MilvusException(1100, f"IVF_FLAT search refused: {e}") from None
-            return np.asarray(idx, dtype=np.int64), np.asarray(score, dtype=np.float32)
-        idx, score = c.bank().search(q, k, row_mask=mask) if mask is not None else c.bank().search(q, k)
-        return np.asarray(idx, dtype=np.int64), np.asarray(score, dtype=np.float32)
+            # (refused: the rounds ran out -- never a partial answer)
+            what, method, args = "grouped search", "search_grouped", (q, want, gs)
+            kwargs = dict(groups=codes, n_groups=n_groups, radius=radius, range_filter=range_filter, row_mask=mask)
+        else:
+            k = min(int(limit), c.n_live)
+            if k > KNN_MAX_K:
+                # pymilvus accepts limit up to 16384; the reference asks for 1 or 3 (milvus/search_json.py:411,
+                # milvus/search_embeddings.py:64).  Here: 32 certified hits per selection pass, at most 32 passes.
+                raise MilvusException(1100, f"limit {limit} is not supported by this build: at most {KNN_MAX_K} hits per query "
+                                            f"(collection holds {c.n_live} rows)")
+            if self._use_index and c.ivf_nlist() is not None:      # (grouped and ranged searches stay on the brute-force path above)
+                nprobe = self._nprobe_of(search_params, param)
+                c.bank()
+                c.sync_index()
+                # (refused: more than 1024 lists to probe -- never answered by another search)
+                what, method, args, kwargs = "IVF_FLAT search", "search_ivf", (q, k, nprobe), dict(row_mask=mask)
+            else:           # what = None: an error of the plain search is passed on as it is.  Unfiltered, it is search(q, k) and no more
+                what, method, args, kwargs = None, "search", (q, k), ({} if mask is None else dict(row_mask=mask))
+        try:
+            idx, score = getattr(c.bank(), method)(*args, **kwargs)
+        except AsttsError as e:
+            if what is None:
+                raise
+            raise MilvusException(1100, f"{what} refused: {e}") from None
+        return np.asarray(idx, dtype=np.int64)[:, skip:], np.asarray(score, dtype=np.float32)[:, skip:]
 
     def hits_from_rows(self, collection_name: str, idx, score, output_fields: Optional[Sequence[str]] = None,
                        group_by_field: Optional[str] = None) -> List[List[Dict[str, Any]]]:

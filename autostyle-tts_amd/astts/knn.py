@@ -7,7 +7,7 @@ replaces what the reference gets from milvus-lite for
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Optional
 
 import numpy as np
 import torch
@@ -47,6 +47,78 @@ def _require_gpu() -> None:
     if not torch.cuda.is_available():
         raise RuntimeError("astts.knn needs a ROCm GPU (torch.cuda.is_available() is False); "
                            "there is no CPU fallback in the product path")
+
+
+# ---- what every search form shares: queries, outputs, row mask, workspace, host conversion
+def _as_queries(queries: torch.Tensor, d: int, device: torch.device) -> torch.Tensor:
+    """``queries`` as the ABI takes them: fp32, contiguous ``[Q, d]`` on ``device`` (a tensor that already is, is passed as is)."""
+    if queries.dim() != 2 or queries.shape[1] != d:
+        raise ValueError(f"queries must be [Q, {d}], got {tuple(queries.shape)}")
+    if queries.dtype != torch.float32 or queries.device != device or not queries.is_contiguous():
+        return queries.to(device=device, dtype=torch.float32).contiguous()
+    return queries
+
+
+def _outputs(nq: int, columns: int, return_f64: bool, device: torch.device, out_idx=None, out_score=None):
+    """-> (idx int64, score fp32, score fp64 or None), each ``[nq, columns]`` on ``device``; a caller's ``out_idx`` / ``out_score``
+    are used in place of new ones (an empty search returns new empties)."""
+    if out_idx is None or nq == 0:
+        out_idx = torch.empty((nq, columns), dtype=torch.int64, device=device)
+    if out_score is None or nq == 0:
+        out_score = torch.empty((nq, columns), dtype=torch.float32, device=device)
+    return out_idx, out_score, torch.empty((nq, columns), dtype=torch.float64, device=device) if return_f64 else None
+
+
+def _row_mask(row_mask: Optional[torch.Tensor], nq: int, n: int, device: torch.device):
+    """-> (the uint8 mask on ``device`` -- to be kept referenced across the call --, its pointer, its stride per query): ``[n]`` is one
+    mask for every query (stride 0), ``[nq, n]`` one per query (stride ``n``); without a mask (None, None, 0)."""
+    if row_mask is None:
+        return None, None, 0
+    m = row_mask.to(device=device)
+    m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
+    if m.shape != (n,) and m.shape != (nq, n):
+        raise ValueError(f"row_mask must be [{n}] or [{nq}, {n}], got {tuple(m.shape)}")
+    return m, m.data_ptr(), 0 if m.dim() == 1 else n
+
+
+class _Workspace:
+    """The device buffer one search form works in: it grows to the largest search seen, and the calls get its 256-byte aligned
+    base and the bytes behind it.  Nothing outside holds a pointer into it, so replacing the buffer leaves nothing stale."""
+
+    def __init__(self, device: torch.device):
+        self.device = device
+        self.buf: Optional[torch.Tensor] = None
+        self.base = self.nbytes = 0
+        self.fits = set()                            # the search shapes the buffer is known to hold
+
+    def fit(self, key: tuple, invalid, sizing, *handles):
+        """Room for a search of shape ``key``, which needs ``sizing(*handles, *key)`` bytes (asked once per shape; 0: the library
+        refuses the shape -> ``ValueError(invalid())``).  -> (aligned base, bytes behind it)."""
+        if key not in self.fits:
+            need = int(sizing(*handles, *key))
+            if need == 0:
+                raise ValueError(invalid())
+            if self.buf is None or self.buf.numel() < need + 256:      # (+ 256: the aligned part holds ``need`` wherever the buffer starts)
+                self.buf = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                start = self.buf.data_ptr()
+                self.base = (start + 255) // 256 * 256
+                self.nbytes = self.buf.numel() - (self.base - start)
+            self.fits.add(key)
+        return self.base, self.nbytes
+
+    def forget(self) -> None:
+        """The sizes are per (rows, tombstone state, index): ask again, keep the buffer."""
+        self.fits.clear()
+
+
+def _host_inputs(queries, row_mask, device: torch.device):
+    """numpy / lists -> (queries fp32 ``[Q, D]`` on ``device`` -- one ``[D]`` vector is one query --, row mask uint8 tensor or None)."""
+    q = torch.as_tensor(np.asarray(queries, dtype=np.float32))
+    if q.dim() == 1:
+        q = q[None, :]
+    if row_mask is not None and not isinstance(row_mask, torch.Tensor):
+        row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
+    return q.to(device), row_mask
 
 
 class StyleBank:
@@ -93,28 +165,35 @@ class StyleBank:
         self._h = h
         self.metric = metric.upper()
         self.d = int(src.shape[1])
-        self._ws: Optional[torch.Tensor] = None
-        self._ws_key: Tuple[int, int] = (0, 0)
-        self._plans: dict = {}                       # (nq, k) -> (workspace tensor, aligned pointer, bytes)
-        self._gws: Optional[torch.Tensor] = None     # the grouped search's workspace and its plans per (nq, limit, group_size, n_groups)
-        self._gplans: dict = {}
+        self._index = int(self.device.index)
+        self._ws = _Workspace(self.device)           # the plain search's, sized per (nq, k); last_fallbacks reads it
+        self._gws = _Workspace(self.device)          # the grouped search's, per (nq, limit, group_size, n_groups)
+        self._iws = _Workspace(self.device)          # the IVF search's, per (nq, k, nprobe)
         self.last_rounds = 0                         # rounds the last grouped search took (rounds_host)
-        self._ivf = None                             # astts_knn_ivf_t* (build_index), its workspace and its plans per (nq, k, nprobe)
-        self._iws: Optional[torch.Tensor] = None
-        self._iplans: dict = {}
-        self._search = lib.astts_knn_search
+        self._ivf = None                             # astts_knn_ivf_t* (build_index)
+        self._search, self._search_bytes = lib.astts_knn_search, lib.astts_knn_workspace_bytes
         self._refresh()
 
     def _refresh(self) -> None:
-        """``n``, ``live``, ``capacity`` and ``scan_plane_exact`` from the handle; the workspace plans are per (n, tombstone state)."""
+        """``n``, ``live``, ``capacity`` and ``scan_plane_exact`` from the handle; the workspaces forget which search shapes fit (the sizes are per n and
+        tombstone state)."""
         n, live, cap, exact = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
         _lib.check(_lib_knn.load().astts_knn_stats(self._h, ctypes.byref(n), ctypes.byref(live), ctypes.byref(cap)))
         _lib.check(_lib.load().astts_knn_info(self._h, None, None, ctypes.byref(exact)))
         self.n, self.live, self.capacity = int(n.value), int(live.value), int(cap.value)
         self.scan_plane_exact = bool(exact.value)
-        self._plans = {}
-        self._gplans = {}
-        self._iplans = {}
+        for ws in (self._ws, self._gws, self._iws):
+            ws.forget()
+
+    def _enter(self) -> Optional[int]:
+        """Make the bank's device the current one for a call: -> the device to go back to afterwards, None when it was current
+        already (the usual case, which then costs one comparison: ``with torch.cuda.device`` is too slow for a 12 us search).  The
+        caller restores it in a ``finally``: ``if prev is not None: torch.cuda.set_device(prev)``."""
+        prev = torch.cuda.current_device()
+        if prev == self._index:
+            return None
+        torch.cuda.set_device(self._index)
+        return prev
 
     # ---- mutation (each call synchronises the current stream, as the constructor does)
     def reserve(self, capacity: int) -> None:
@@ -185,15 +264,6 @@ class StyleBank:
         except Exception:
             pass
 
-    def _workspace(self, nq: int, k: int) -> torch.Tensor:
-        need = int(_lib.load().astts_knn_workspace_bytes(self._h, nq, k))
-        if need == 0:
-            raise ValueError(f"invalid search shape nq={nq} k={k}")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._plans = {}                         # (plans of the smaller workspace point into freed memory)
-        return self._ws
-
     def search_device(self, queries: torch.Tensor, k: int, force_exact: bool = False,
                       out_idx: Optional[torch.Tensor] = None, out_score: Optional[torch.Tensor] = None, return_f64: bool = False,
                       row_mask: Optional[torch.Tensor] = None):
@@ -202,65 +272,33 @@ class StyleBank:
         squared distance ascending; ties by row index).  ``return_f64``: a third tensor with the fp64 scores (what a
         bank-sharded search merges on: astts.parallel.bank_sharded_search).  ``row_mask``: uint8 / bool ``[N]`` (one mask for
         every query) or ``[Q, N]`` on the GPU -- only rows with a non-zero entry can be hits (a Milvus ``filter``)."""
-        if queries.dim() != 2 or queries.shape[1] != self.d:
-            raise ValueError(f"queries must be [Q, {self.d}], got {tuple(queries.shape)}")
+        q = _as_queries(queries, self.d, self.device)
         if not 1 <= k <= _lib.KNN_MAX_K:
             raise ValueError(f"k must be in 1..{_lib.KNN_MAX_K}, got {k}")
         # (a config-2 search is ~12 us of GPU time: the host side of this call is kept to a handful of attribute reads and ONE ctypes
-        # call -- the workspace and its size are cached per (queries, k), tensors that already are what the ABI takes are passed as is)
-        q = queries
-        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
-            q = queries.to(device=self.device, dtype=torch.float32).contiguous()
+        # call -- the workspace's size is asked once per (queries, k), tensors that already are what the ABI takes are passed as is)
         nq = int(q.shape[0])
-        if nq == 0:
-            e = (torch.empty((0, k), dtype=torch.int64, device=self.device), torch.empty((0, k), dtype=torch.float32, device=self.device))
-            return e + (torch.empty((0, k), dtype=torch.float64, device=self.device),) if return_f64 else e
-        switch = torch.cuda.current_device() != self.device.index
-        if switch:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(self.device)
-        try:
-            plan = self._plans.get((nq, k))
-            if plan is None:
-                ws = self._workspace(nq, k)
-                base = ws.data_ptr()
-                aligned = (base + 255) // 256 * 256
-                plan = self._plans[(nq, k)] = (ws, aligned, ws.numel() - (aligned - base))
-            ws, aligned, ws_bytes = plan
-            if out_idx is None:
-                out_idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-            if out_score is None:
-                out_score = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-            s64 = torch.empty((nq, k), dtype=torch.float64, device=self.device) if return_f64 else None
-            mptr, mstride = None, 0
-            if row_mask is not None:
-                m = row_mask.to(device=self.device)
-                m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
-                if m.shape == (self.n,):
-                    mstride = 0
-                elif m.shape == (nq, self.n):
-                    mstride = self.n
-                else:
-                    raise ValueError(f"row_mask must be [{self.n}] or [{nq}, {self.n}], got {tuple(m.shape)}")
-                mptr = m.data_ptr()
-            rc = self._search(self._h, q.data_ptr(), nq, k, out_idx.data_ptr(), out_score.data_ptr(), None if s64 is None else s64.data_ptr(),
-                              mptr, mstride, aligned, ws_bytes, _lib.KNN_FORCE_EXACT if force_exact else 0,
-                              torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                _lib.check(rc)
-        finally:
-            if switch:
-                torch.cuda.set_device(prev)
-        return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+        out = _outputs(nq, k, return_f64, self.device, out_idx, out_score)
+        out_idx, out_score, s64 = out
+        if nq:
+            prev = self._enter()
+            try:
+                base, ws_bytes = self._ws.fit((nq, k), lambda: f"invalid search shape nq={nq} k={k}", self._search_bytes, self._h)
+                m, mptr, mstride = _row_mask(row_mask, nq, self.n, self.device)
+                rc = self._search(self._h, q.data_ptr(), nq, k, out_idx.data_ptr(), out_score.data_ptr(), None if s64 is None else s64.data_ptr(),
+                                  mptr, mstride, base, ws_bytes, _lib.KNN_FORCE_EXACT if force_exact else 0,
+                                  torch.cuda.current_stream(self._index).cuda_stream)
+                if rc != 0:
+                    _lib.check(rc)
+            finally:
+                if prev is not None:
+                    torch.cuda.set_device(prev)
+        return out if return_f64 else out[:2]
 
     def search(self, queries, k: int, force_exact: bool = False, row_mask=None):
         """Host convenience: accepts numpy / lists, returns numpy (idx int64 [Q,k], score fp32 [Q,k])."""
-        q = torch.as_tensor(np.asarray(queries, dtype=np.float32))
-        if q.dim() == 1:
-            q = q[None, :]
-        if row_mask is not None and not isinstance(row_mask, torch.Tensor):
-            row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
-        idx, sc = self.search_device(q.to(self.device), k, force_exact, row_mask=row_mask)
+        q, row_mask = _host_inputs(queries, row_mask, self.device)
+        idx, sc = self.search_device(q, k, force_exact, row_mask=row_mask)
         return idx.cpu().numpy(), sc.cpu().numpy()
 
     # ---- grouped and ranged search (include/knn/astts_knn_grouped.h)
@@ -278,76 +316,52 @@ class StyleBank:
         its own group.  ``radius`` / ``range_filter``: COSINE / IP ``radius < score <= range_filter``, L2
         ``range_filter <= distance < radius``.  Runs on the current stream and SYNCHRONISES it once per round (one round when the
         first 32 hits settle every query; ``last_rounds`` tells how many it took; ``max_rounds`` 0 = 64, beyond it the call raises)."""
-        if queries.dim() != 2 or queries.shape[1] != self.d:
-            raise ValueError(f"queries must be [Q, {self.d}], got {tuple(queries.shape)}")
+        q = _as_queries(queries, self.d, self.device)
         limit, group_size = int(limit), int(group_size)
         if limit < 1 or group_size < 1 or limit * group_size > _lib.KNN_MAX_K:
             raise ValueError(f"limit * group_size must be in 1..{_lib.KNN_MAX_K}, got {limit} x {group_size}")
-        slots = limit * group_size
-        q = queries
-        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
-            q = queries.to(device=self.device, dtype=torch.float32).contiguous()
         nq = int(q.shape[0])
-        out_idx = torch.empty((nq, slots), dtype=torch.int64, device=self.device)
-        out_score = torch.empty((nq, slots), dtype=torch.float32, device=self.device)
-        s64 = torch.empty((nq, slots), dtype=torch.float64, device=self.device) if return_f64 else None
+        out = _outputs(nq, limit * group_size, return_f64, self.device)
+        out_idx, out_score, s64 = out
         self.last_rounds = 0
-        if nq == 0:
-            return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
-        lib = _lib_knn_grouped.load()
-        with torch.cuda.device(self.device):
-            gptr, ng = None, 1
-            if groups is not None:
-                if groups.shape != (self.n,) or groups.dtype != torch.int32 or groups.device != self.device:
-                    raise ValueError(f"groups must be int32 [{self.n}] on {self.device}, got {groups.dtype} {tuple(groups.shape)} on {groups.device}")
-                groups = groups.contiguous()
-                ng = int(n_groups) if n_groups is not None else int(groups.max()) + 1
-                gptr = groups.data_ptr()
-            key = (nq, limit, group_size, ng if groups is not None else 0)
-            plan = self._gplans.get(key)
-            if plan is None:
-                need = int(lib.astts_knn_grouped_workspace_bytes(self._h, *key))
-                if need == 0:
-                    raise ValueError(f"invalid grouped search shape nq={nq} limit={limit} group_size={group_size} n_groups={ng} (n={self.n})")
-                if self._gws is None or self._gws.numel() < need + 256:
-                    self._gws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                    self._gplans = {}
-                base = self._gws.data_ptr()
-                aligned = (base + 255) // 256 * 256
-                plan = self._gplans[key] = (self._gws, aligned, self._gws.numel() - (aligned - base))
-            _, aligned, ws_bytes = plan
-            mptr, mstride = None, 0
-            if row_mask is not None:
-                m = row_mask.to(device=self.device)
-                m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
-                if m.shape == (self.n,):
-                    mstride = 0
-                elif m.shape == (nq, self.n):
-                    mstride = self.n
-                else:
-                    raise ValueError(f"row_mask must be [{self.n}] or [{nq}, {self.n}], got {tuple(m.shape)}")
-                mptr = m.data_ptr()
-            rad = None if radius is None else ctypes.c_double(float(radius))
-            rf = None if range_filter is None else ctypes.c_double(float(range_filter))
-            rounds = ctypes.c_int32()
-            rc = lib.astts_knn_search_grouped(self._h, q.data_ptr(), nq, limit, group_size, gptr, ng,
-                                              None if rad is None else ctypes.addressof(rad), None if rf is None else ctypes.addressof(rf),
-                                              out_idx.data_ptr(), out_score.data_ptr(), None if s64 is None else s64.data_ptr(),
-                                              mptr, mstride, aligned, ws_bytes, _lib.KNN_FORCE_EXACT if force_exact else 0, int(max_rounds),
-                                              ctypes.addressof(rounds), torch.cuda.current_stream(self.device).cuda_stream)
-            self.last_rounds = int(rounds.value)
-            if rc != 0:
-                _lib.check(rc)
-        return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+        if nq:
+            lib = _lib_knn_grouped.load()
+            prev = self._enter()
+            try:
+                gptr, ng = None, 1
+                if groups is not None:
+                    if groups.shape != (self.n,) or groups.dtype != torch.int32 or groups.device != self.device:
+                        raise ValueError(f"groups must be int32 [{self.n}] on {self.device}, got {groups.dtype} {tuple(groups.shape)} on {groups.device}")
+                    groups = groups.contiguous()
+                    ng = int(n_groups) if n_groups is not None else int(groups.max()) + 1
+                    gptr = groups.data_ptr()
+                base, ws_bytes = self._gws.fit(
+                    (nq, limit, group_size, ng if groups is not None else 0),
+                    lambda: f"invalid grouped search shape nq={nq} limit={limit} group_size={group_size} n_groups={ng} (n={self.n})",
+                    lib.astts_knn_grouped_workspace_bytes, self._h)
+                m, mptr, mstride = _row_mask(row_mask, nq, self.n, self.device)
+                rad = None if radius is None else ctypes.c_double(float(radius))
+                rf = None if range_filter is None else ctypes.c_double(float(range_filter))
+                rounds = ctypes.c_int32()
+                rc = lib.astts_knn_search_grouped(self._h, q.data_ptr(), nq, limit, group_size, gptr, ng,
+                                                  None if rad is None else ctypes.addressof(rad), None if rf is None else ctypes.addressof(rf),
+                                                  out_idx.data_ptr(), out_score.data_ptr(), None if s64 is None else s64.data_ptr(),
+                                                  mptr, mstride, base, ws_bytes, _lib.KNN_FORCE_EXACT if force_exact else 0, int(max_rounds),
+                                                  ctypes.addressof(rounds), torch.cuda.current_stream(self._index).cuda_stream)
+                self.last_rounds = int(rounds.value)
+                if rc != 0:
+                    _lib.check(rc)
+            finally:
+                if prev is not None:
+                    torch.cuda.set_device(prev)
+        return out if return_f64 else out[:2]
 
     def search_grouped(self, queries, limit: int, group_size: int = 1, groups=None, n_groups: Optional[int] = None,
                        radius: Optional[float] = None, range_filter: Optional[float] = None, row_mask=None, force_exact: bool = False,
                        max_rounds: int = 0):
         """Host convenience of ``search_grouped_device``: accepts numpy / lists (``groups``: integer codes ``[N]``, checked to lie in
         ``[0, n_groups)``), returns numpy (idx int64, score fp32 ``[Q, limit * group_size]``)."""
-        q = torch.as_tensor(np.asarray(queries, dtype=np.float32))
-        if q.dim() == 1:
-            q = q[None, :]
+        q, row_mask = _host_inputs(queries, row_mask, self.device)
         if groups is not None and not isinstance(groups, torch.Tensor):
             g = np.ascontiguousarray(np.asarray(groups).reshape(-1).astype(np.int64))
             if n_groups is None:
@@ -355,9 +369,7 @@ class StyleBank:
             if g.size != self.n or (g.size and (g.min() < 0 or g.max() >= n_groups)):
                 raise ValueError(f"groups must be {self.n} codes in [0, {n_groups})")
             groups = torch.from_numpy(g.astype(np.int32)).to(self.device)
-        if row_mask is not None and not isinstance(row_mask, torch.Tensor):
-            row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
-        idx, sc = self.search_grouped_device(q.to(self.device), limit, group_size, groups, n_groups, radius, range_filter, row_mask,
+        idx, sc = self.search_grouped_device(q, limit, group_size, groups, n_groups, radius, range_filter, row_mask,
                                              force_exact, max_rounds=max_rounds)
         return idx.cpu().numpy(), sc.cpu().numpy()
 
@@ -388,7 +400,7 @@ class StyleBank:
         if self._ivf is not None:
             _lib_knn_ivf.load().astts_knn_ivf_destroy(self._ivf)
             self._ivf = None
-        self._iplans = {}
+        self._iws.forget()
 
     def index_info(self) -> Optional[dict]:
         """None without an index, else ``{"index_type": "IVF_FLAT", "nlist", "n_indexed", "max_list_len"}`` (``nlist``: the lists that
@@ -418,64 +430,37 @@ class StyleBank:
         no synchronisation."""
         if self._ivf is None:
             raise RuntimeError("the bank has no index: build_index first (there is no quiet fall-back to the brute-force search)")
-        if queries.dim() != 2 or queries.shape[1] != self.d:
-            raise ValueError(f"queries must be [Q, {self.d}], got {tuple(queries.shape)}")
+        q = _as_queries(queries, self.d, self.device)
         k, nprobe = int(k), int(nprobe)
         if not 1 <= k <= _lib.KNN_MAX_K:
             raise ValueError(f"k must be in 1..{_lib.KNN_MAX_K}, got {k}")
         if nprobe < 1:
             raise ValueError(f"nprobe must be >= 1, got {nprobe}")
-        q = queries
-        if q.dtype != torch.float32 or q.device != self.device or not q.is_contiguous():
-            q = queries.to(device=self.device, dtype=torch.float32).contiguous()
         nq = int(q.shape[0])
-        out_idx = torch.empty((nq, k), dtype=torch.int64, device=self.device)
-        out_score = torch.empty((nq, k), dtype=torch.float32, device=self.device)
-        s64 = torch.empty((nq, k), dtype=torch.float64, device=self.device) if return_f64 else None
-        if nq == 0:
-            return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
-        lib = _lib_knn_ivf.load()
-        with torch.cuda.device(self.device):
-            key = (nq, k, nprobe)
-            plan = self._iplans.get(key)
-            if plan is None:
-                need = int(lib.astts_knn_ivf_workspace_bytes(self._ivf, self._h, nq, k, nprobe))
-                if need == 0:
-                    raise ValueError(f"invalid IVF search shape nq={nq} k={k} nprobe={nprobe}")
-                if self._iws is None or self._iws.numel() < need + 256:
-                    self._iws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                    self._iplans = {}
-                base = self._iws.data_ptr()
-                aligned = (base + 255) // 256 * 256
-                plan = self._iplans[key] = (self._iws, aligned, self._iws.numel() - (aligned - base))
-            _, aligned, ws_bytes = plan
-            mptr, mstride = None, 0
-            if row_mask is not None:
-                m = row_mask.to(device=self.device)
-                m = (m if m.dtype == torch.uint8 else (m != 0).to(torch.uint8)).contiguous()
-                if m.shape == (self.n,):
-                    mstride = 0
-                elif m.shape == (nq, self.n):
-                    mstride = self.n
-                else:
-                    raise ValueError(f"row_mask must be [{self.n}] or [{nq}, {self.n}], got {tuple(m.shape)}")
-                mptr = m.data_ptr()
-            rc = lib.astts_knn_ivf_search(self._ivf, self._h, q.data_ptr(), nq, k, nprobe, out_idx.data_ptr(), out_score.data_ptr(),
-                                          None if s64 is None else s64.data_ptr(), mptr, mstride, aligned, ws_bytes,
-                                          torch.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                _lib.check(rc)
-        return (out_idx, out_score, s64) if return_f64 else (out_idx, out_score)
+        out = _outputs(nq, k, return_f64, self.device)
+        out_idx, out_score, s64 = out
+        if nq:
+            lib = _lib_knn_ivf.load()
+            prev = self._enter()
+            try:
+                base, ws_bytes = self._iws.fit((nq, k, nprobe), lambda: f"invalid IVF search shape nq={nq} k={k} nprobe={nprobe}",
+                                               lib.astts_knn_ivf_workspace_bytes, self._ivf, self._h)
+                m, mptr, mstride = _row_mask(row_mask, nq, self.n, self.device)
+                rc = lib.astts_knn_ivf_search(self._ivf, self._h, q.data_ptr(), nq, k, nprobe, out_idx.data_ptr(), out_score.data_ptr(),
+                                              None if s64 is None else s64.data_ptr(), mptr, mstride, base, ws_bytes,
+                                              torch.cuda.current_stream(self._index).cuda_stream)
+                if rc != 0:
+                    _lib.check(rc)
+            finally:
+                if prev is not None:
+                    torch.cuda.set_device(prev)
+        return out if return_f64 else out[:2]
 
     def search_ivf(self, queries, k: int, nprobe: int = _lib_knn_ivf.DEFAULT_NPROBE, row_mask=None, return_f64: bool = False):
         """Host convenience of ``search_ivf_device``: accepts numpy / lists, returns numpy (idx int64 [Q,k], score fp32 [Q,k] and,
         with ``return_f64``, score fp64 [Q,k])."""
-        q = torch.as_tensor(np.asarray(queries, dtype=np.float32))
-        if q.dim() == 1:
-            q = q[None, :]
-        if row_mask is not None and not isinstance(row_mask, torch.Tensor):
-            row_mask = torch.from_numpy(np.ascontiguousarray(np.asarray(row_mask) != 0).astype(np.uint8))
-        out = self.search_ivf_device(q.to(self.device), k, nprobe, row_mask=row_mask, return_f64=return_f64)
+        q, row_mask = _host_inputs(queries, row_mask, self.device)
+        out = self.search_ivf_device(q, k, nprobe, row_mask=row_mask, return_f64=return_f64)
         return tuple(t.cpu().numpy() for t in out)
 
     def route(self, nq: int, k: int, masked: bool = False, aligned: bool = True):
@@ -485,13 +470,11 @@ class StyleBank:
 
     def last_fallbacks(self) -> int:
         """How many queries of the last search needed the exact fp64 scan (synchronises)."""
-        if self._ws is None:
+        if self._ws.buf is None:
             return 0
-        base = self._ws.data_ptr()
-        aligned = (base + 255) // 256 * 256
         out = ctypes.c_int32()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().astts_knn_last_fallbacks(self._h, aligned, _lib.stream_ptr(), ctypes.byref(out)))
+            _lib.check(_lib.load().astts_knn_last_fallbacks(self._h, self._ws.base, _lib.stream_ptr(), ctypes.byref(out)))
         return int(out.value)
 
     # ---- bench-only: time the scan kernel with HIP events on the search stream
