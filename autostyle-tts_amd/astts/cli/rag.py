@@ -29,6 +29,7 @@ from glob import glob
 import numpy as np
 
 from astts.cli.search_json import embed_rows, generate_speaker_biographies
+from astts.cli.search_milvus import EMBED_MODEL_HELP
 from astts.compat.pymilvus import MilvusClient
 
 COLLECTION = "embeddings_biographies_collection"          # RAG.py:457
@@ -105,7 +106,9 @@ def main(args, client=None, embedder=None):
         from astts.cli.search_milvus import load_embedder
         embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed, getattr(args, "base_model_path", None),
                                  getattr(args, "llm_precision", None))
-    dim = 2 * embedder.cfg.hidden                                                                   # :458
+    from astts.cli.search_milvus import load_text_encoder
+    encoder = load_text_encoder(args) or embedder        # --embed_model_path: the sentence encoder embeds, the LLM only generates
+    dim = 2 * encoder.cfg.hidden                                                                    # :458
     client = client or MilvusClient(args.db_path)
     if client.has_collection(collection_name=COLLECTION):                                           # :49-51
         client.drop_collection(collection_name=COLLECTION)
@@ -117,7 +120,7 @@ def main(args, client=None, embedder=None):
     conv = {s: "\n".join(u["text"] for u in utts) for s, utts in speakers.items()}               # :484
     bios = generate_speaker_biographies(conv, embedder, args.max_new_tokens, batch, args.seed)
     flat = [{"speaker": s, "zh_text": u["text"], "file_id": u["file_id"], "pk": i + 1} for s, utts in speakers.items() for i, u in enumerate(utts)]
-    q, labels, failed = embed_rows(flat, embedder, bios, max_new_tokens=10, batch=batch)
+    q, labels, failed = embed_rows(flat, embedder, bios, max_new_tokens=10, batch=batch, encoder=encoder)
     results, insert = [], []
     for r, vec, lab, bad in zip(flat, q, labels, failed):
         if bad:
@@ -158,7 +161,7 @@ def main(args, client=None, embedder=None):
         print(f"\nPerforming search for the input text: '{args.search_text}'")
         try:
             first = next(iter(speakers))
-            sq, slab, sbad = embed_rows([{"zh_text": args.search_text, "speaker": first}], embedder, bios, max_new_tokens=10, batch=1)
+            sq, slab, sbad = embed_rows([{"zh_text": args.search_text, "speaker": first}], embedder, bios, max_new_tokens=10, batch=1, encoder=encoder)
             if sbad[0]:
                 raise RuntimeError("no embedding for the search text")
             found = client.search(collection_name=COLLECTION, data=sq, limit=args.top_k, filter=None, output_fields=["file_id", "text"])
@@ -179,6 +182,7 @@ def build_parser():
     p.add_argument("--model_path", type=str, default="", help="Llama-3.2-3B directory: a PEFT LoRA adapter (LLM.int8 + LoRA, as the reference) "
                    "or merged weights + tokenizer")
     p.add_argument("--base_model_path", default=None, help="base checkpoint directory of a LoRA adapter (local only; nothing is fetched)")
+    p.add_argument("--embed_model_path", default="", help=EMBED_MODEL_HELP)
     p.add_argument("--llm_precision", choices=("int8", "fp16"), default=None,
                    help="embedder weights: default int8 for an adapter directory, fp16 for merged weights")
     p.add_argument("--allow_random_init", action="store_true", help="run on seeded random Llama weights when model_path does not exist")

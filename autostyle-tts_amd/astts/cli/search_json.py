@@ -38,6 +38,7 @@ import traceback
 import numpy as np
 
 from astts import parallel
+from astts.cli.search_milvus import EMBED_MODEL_HELP
 from astts.compat.pymilvus import MilvusClient
 
 
@@ -108,12 +109,14 @@ def write_biographies(path, biographies):
         json.dump(biographies, f, ensure_ascii=False, indent=2)
 
 
-def embed_rows(rows, embedder, biographies, max_new_tokens=10, batch=32):
+def embed_rows(rows, embedder, biographies, max_new_tokens=10, batch=32, encoder=None):
     """milvus/search_json.py:382-411 for a list of rows -> (queries float32 [n, 2 * hidden], labels, failed bool [n]).  The labels come
     from batched KV-cached greedy decodes (``batch`` rows at a time, sorted by prompt length so that the left padding stays small); each
     DISTINCT label / biography text is embedded once (the reference re-embeds them per row: same vectors).  Failures keep the reference's
     per-row semantics (milvus/search_json.py:389-404): a label that cannot be generated becomes "neutral", a row whose embedding fails is
-    marked ``failed`` (its record says "Error") -- the other rows of the shard go on."""
+    marked ``failed`` (its record says "Error") -- the other rows of the shard go on.  ``encoder`` (``--embed_model_path``): the model
+    that embeds; ``embedder`` then only generates the labels."""
+    encoder = embedder if encoder is None else encoder
     texts = [r.get("zh_text", "").strip() for r in rows]
     labels = [None] * len(rows)
     order = sorted(range(len(rows)), key=lambda i: len(texts[i]))
@@ -132,11 +135,11 @@ def embed_rows(rows, embedder, biographies, max_new_tokens=10, batch=32):
     for c0 in range(0, len(uniq), batch):
         chunk = uniq[c0:c0 + batch]
         try:
-            for t, e in zip(chunk, embedder.get_embeddings(chunk)):
+            for t, e in zip(chunk, encoder.get_embeddings(chunk)):
                 vec[t] = e
         except Exception as e:  # noqa: BLE001
             print(f"Error getting embedding: {e}")
-    h = embedder.cfg.hidden
+    h = encoder.cfg.hidden
     q = np.zeros((len(rows), 2 * h), np.float32)
     failed = np.zeros(len(rows), bool)
     for i in range(len(rows)):
@@ -182,8 +185,9 @@ def main(args, client=None, embedder=None):
                 from astts.cli.search_milvus import load_embedder
                 embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed,
                                          getattr(args, "base_model_path", None), getattr(args, "llm_precision", None))
-            from astts.cli.search_milvus import check_query_dim
-            check_query_dim(client, args.collection_name, 2 * embedder.cfg.hidden)
+            from astts.cli.search_milvus import check_query_dim, load_text_encoder
+            encoder = load_text_encoder(args) or embedder
+            check_query_dim(client, args.collection_name, 2 * encoder.cfg.hidden)
             bios = load_biographies(getattr(args, "biography_json", ""))
         if getattr(args, "generate_biographies", False):
             # rank 0 samples the biographies of the speakers the file does not cover (all rows' speakers, not its shard's) and every
@@ -198,8 +202,8 @@ def main(args, client=None, embedder=None):
         with parallel.rank_work(dist, "search_json: emotion label + embedding"):
             if getattr(args, "biography_out", "") and rank == 0:
                 write_biographies(args.biography_out, bios)
-            q, labels, failed_local = embed_rows(rows[b0:b1], embedder, bios, max_new_tokens=10, batch=getattr(args, "llm_batch", 32))
-        full = np.zeros((len(rows), q.shape[1] if len(q) else 2 * embedder.cfg.hidden), np.float32)
+            q, labels, failed_local = embed_rows(rows[b0:b1], embedder, bios, max_new_tokens=10, batch=getattr(args, "llm_batch", 32), encoder=encoder)
+        full = np.zeros((len(rows), q.shape[1] if len(q) else 2 * encoder.cfg.hidden), np.float32)
         full[b0:b1] = q
         q = full
         if rank == 0 and getattr(args, "verbose", False):
@@ -267,6 +271,7 @@ def build_parser():
     p.add_argument("--model_path", "--llm_dir", dest="model_path", default="", help="Llama-3.2-3B directory: a PEFT LoRA adapter (LLM.int8 + "
                    "LoRA, as the reference) or merged weights + tokenizer: the reference's --model_path (milvus/search_json.py:469)")
     p.add_argument("--base_model_path", default=None, help="base checkpoint directory of a LoRA adapter (local only; nothing is fetched)")
+    p.add_argument("--embed_model_path", default="", help=EMBED_MODEL_HELP)
     p.add_argument("--llm_precision", choices=("int8", "fp16"), default=None,
                    help="embedder weights: default int8 for an adapter directory, fp16 for merged weights")
     p.add_argument("--biography_json", default="", help="{speaker: biography} (the reference samples these from the LLM; absent speakers "

@@ -23,7 +23,7 @@ speaker_bio = {
 }
 
 
-TOKENIZER_FILES = ("tokenizer.json", "tokenizer.model", "vocab.json", "tokenizer_config.json")
+TOKENIZER_FILES = ("tokenizer.json", "tokenizer.model", "vocab.json", "tokenizer_config.json", "vocab.txt", "sentencepiece.bpe.model")
 
 
 def load_tokenizer(model_path):
@@ -49,8 +49,16 @@ def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=
     (``base_model_path``, else the adapter's base_model_name_or_path as a local directory or hub-cache snapshot; never fetched) and
     runs LLM.int8 + the unmerged LoRA branch, the reference's numerics; a merged checkpoint runs fp16.  ``precision`` ("int8" /
     "fp16") overrides either default.  The shape comes from the directory's config.json (Llama, Qwen2 or Qwen3; astts.llm.peft.shape_from_config).  Without a directory this raises unless random-init weights are explicitly allowed
-    (plumbing runs, benchmarks)."""
+    (plumbing runs, benchmarks).
+
+    A directory whose config.json says model_type bert, roberta or xlm-roberta (m3e, bge, multilingual-e5; a sentence-transformers
+    directory or a plain transformers one) is a sentence ENCODER and loads as an astts.llm.encoder_bert.BertEmbedder: the embedding calls
+    of the class above, no generation; the other arguments do not apply to it."""
     import os
+
+    from astts.llm.bert_dir import is_encoder_dir
+    if model_path and os.path.isdir(model_path) and is_encoder_dir(model_path):      # another encoder family: refused there, by model_type
+        return load_bert_embedder(model_path)
 
     from astts.llm.config import LlamaShape
     from astts.llm.embedder import LlamaEmbedder
@@ -80,15 +88,40 @@ def load_embedder(model_path, allow_random_init=False, seed=42, base_model_path=
     return LlamaEmbedder(make_llama_weights(cfg, seed), cfg, int8=precision == "int8")
 
 
+def load_bert_embedder(model_path):
+    """A BERT-family encoder directory -> BertEmbedder: shape from config.json, pooling / normalisation / max_seq_length from the
+    sentence-transformers files when present, the directory's own tokenizer (vocab.txt, tokenizer.json or sentencepiece.bpe.model)."""
+    from astts.llm.bert_dir import bert_shape_from_config, sentence_setup
+    from astts.llm.encoder_bert import BertEmbedder
+    from astts.llm.weights import load_bert_weights
+
+    shape = bert_shape_from_config(model_path)
+    setup = sentence_setup(model_path, shape)
+    return BertEmbedder(load_bert_weights(model_path, shape), shape, tokenizer=load_tokenizer(model_path), setup=setup)
+
+
+def load_text_encoder(args):
+    """``--embed_model_path DIR``: the model that embeds the texts in place of ``--model_path``'s LLM (which then only generates), or
+    None without the flag."""
+    path = getattr(args, "embed_model_path", "")
+    return load_embedder(path) if path else None
+
+
+# --embed_model_path of search_milvus, search_json and rag
+EMBED_MODEL_HELP = ("directory of a sentence encoder (BERT / RoBERTa / XLM-R type: m3e, bge, multilingual-e5) that embeds the texts instead of "
+                    "--model_path's LLM; labels and biographies are still generated by --model_path, and queries and the collection rag "
+                    "creates are 2 x the encoder's hidden size wide")
+
+
 def check_query_dim(client, collection_name, query_dim):
-    """The query is 2 x the embedder's hidden size (6144 for Llama-3.2-3B, 7168 for Qwen2.5-7B); a bank built with another model cannot
+    """The query is 2 x the embedder's hidden size (6144 for Llama-3.2-3B, 7168 for Qwen2.5-7B, 1536 for m3e-base); a bank built with another model cannot
     be searched with it.  One message with both numbers instead of the search's byte count."""
     if not hasattr(client, "get_collection_info") or not client.has_collection(collection_name=collection_name):
         return                                  # a missing collection is reported where it is searched
     fields = client.get_collection_info(collection_name).get("fields", [])
     bank_dim = next((int(f["params"]["dim"]) for f in fields if "dim" in (f.get("params") or {})), None)
     if bank_dim is not None and bank_dim != int(query_dim):
-        raise SystemExit(f"the query embedding has {int(query_dim)} dimensions (2 x the LLM's hidden size {int(query_dim) // 2}) but collection "
+        raise SystemExit(f"the query embedding has {int(query_dim)} dimensions (2 x the embedding model's hidden size {int(query_dim) // 2}) but collection "
                          f"'{collection_name}' holds {bank_dim}-dimensional vectors: this bank was built with another model")
 
 
@@ -109,7 +142,10 @@ def search_milvus(client, collection_name, embedding, top_k=3):
 
 
 def main(args, embedder=None):
-    if embedder is None:
+    encoder = load_text_encoder(args)            # this command only embeds: with --embed_model_path the LLM is not loaded at all
+    if encoder is not None:
+        embedder = encoder
+    elif embedder is None:
         embedder = load_embedder(args.model_path, getattr(args, "allow_random_init", False), args.seed,
                                  getattr(args, "base_model_path", None), getattr(args, "llm_precision", None))
     try:
@@ -163,6 +199,7 @@ def build_parser():
     parser.add_argument("--model_path", type=str, default="",
                         help="Path to the fine-tuned Llama 3.2 model: a PEFT LoRA adapter directory (runs LLM.int8 + LoRA) or merged weights")
     parser.add_argument("--base_model_path", type=str, default=None, help="base checkpoint directory of a LoRA adapter (local only)")
+    parser.add_argument("--embed_model_path", type=str, default="", help=EMBED_MODEL_HELP)
     parser.add_argument("--llm_precision", choices=("int8", "fp16"), default=None,
                         help="embedder weights: default int8 for an adapter directory, fp16 for merged weights")
     parser.add_argument("--allow_random_init", action="store_true",

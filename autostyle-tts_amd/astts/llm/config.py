@@ -1,7 +1,8 @@
 """Shapes of the embedder LLM.  The reference loads "Llama 3.2" 3B (src/search_milvus.py:251-252, milvus/RAG.py:458:
 hidden 3072 -> 2 x 3072 = the 6144-d bank); these are that checkpoint's config.json values.  The same dataclass describes a Qwen2
 checkpoint (the reference's ``_cn`` scripts run Qwen2.5-7B-Instruct): ``model_type``, ``qkv_bias`` and ``rope_type`` carry the differences.
-A Qwen3 checkpoint adds ``qk_norm`` (a per-head RMSNorm of q and k before RoPE) and a ``head_dim`` that is not hidden / heads."""
+A Qwen3 checkpoint adds ``qk_norm`` (a per-head RMSNorm of q and k before RoPE) and a ``head_dim`` that is not hidden / heads.
+``BertShape`` is the other family in front of the style bank: the BERT-type sentence encoders (m3e, bge, e5) of astts.llm.encoder_bert."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -131,3 +132,64 @@ class LlamaShape:
                                   "original_max_position_embeddings": self.rope_original_max_pos, "rope_type": "llama3"},
                     tie_word_embeddings=self.tie_embeddings, attention_bias=False, mlp_bias=False, hidden_act="silu",
                     eos_token_id=self.eos_token_id, bos_token_id=self.bos_token_id, pad_token_id=None)
+
+
+@dataclass(frozen=True)
+class BertShape:
+    """A BERT-family sentence encoder (transformers' BertModel / RobertaModel / XLMRobertaModel without the pooler: post-LayerNorm
+    blocks, learned absolute positions, exact-erf GELU, head dimension 64).  The defaults are m3e-base's config.json ("Moka": bert-base
+    over the 21 128-entry Chinese vocabulary), whose 768-d sentence vector is the style bank's D = 768."""
+    model_type: str = "bert"        # "bert" | "roberta" | "xlm-roberta"
+    vocab: int = 21128
+    hidden: int = 768
+    layers: int = 12
+    heads: int = 12
+    ffn: int = 3072
+    max_positions: int = 512
+    type_vocab: int = 2
+    ln_eps: float = 1e-12
+    pad_token_id: int = 0
+
+    @property
+    def head_dim(self) -> int:
+        return self.hidden // self.heads
+
+    @property
+    def pos_offset(self) -> int:
+        """The position of a row's first token: RoBERTa numbers the real tokens from pad_token_id + 1 (transformers'
+        create_position_ids_from_input_ids; on right-padded rows exactly that), BERT from 0."""
+        return self.pad_token_id + 1 if self.model_type in ("roberta", "xlm-roberta") else 0
+
+    @property
+    def max_tokens(self) -> int:
+        return self.max_positions - self.pos_offset
+
+    @staticmethod
+    def m3e_base() -> "BertShape":
+        return BertShape()
+
+    @staticmethod
+    def bert_tiny() -> "BertShape":
+        """Two heads of 64, two layers, two token types; 160 positions hold the 130-token row that crosses the attention's 128-query tile."""
+        return BertShape(vocab=512, hidden=128, layers=2, heads=2, ffn=512, max_positions=160)
+
+    @staticmethod
+    def xlmr_tiny() -> "BertShape":
+        """``bert_tiny()`` as an XLM-R: one token type, pad_token_id 1, so positions start at 2 and 162 of them hold 160 tokens."""
+        return BertShape(model_type="xlm-roberta", vocab=512, hidden=128, layers=2, heads=2, ffn=512, max_positions=162, type_vocab=1,
+                         ln_eps=1e-5, pad_token_id=1)
+
+    def hf_config(self):
+        """The transformers config of this shape (used only by tests/golden/make_bert_fixtures.py)."""
+        kw = dict(vocab_size=self.vocab, hidden_size=self.hidden, num_hidden_layers=self.layers, num_attention_heads=self.heads,
+                  intermediate_size=self.ffn, hidden_act="gelu", hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
+                  max_position_embeddings=self.max_positions, type_vocab_size=self.type_vocab, layer_norm_eps=self.ln_eps,
+                  pad_token_id=self.pad_token_id)
+        if self.model_type == "bert":
+            from transformers import BertConfig
+            return BertConfig(**kw)
+        if self.model_type == "xlm-roberta":
+            from transformers import XLMRobertaConfig
+            return XLMRobertaConfig(**kw)
+        from transformers import RobertaConfig
+        return RobertaConfig(**kw)

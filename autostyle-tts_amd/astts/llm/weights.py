@@ -4,11 +4,11 @@ from __future__ import annotations
 
 import glob
 import os
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
-from .config import LlamaShape
+from .config import BertShape, LlamaShape
 
 StateDict = Dict[str, torch.Tensor]
 BIAS_OUTLIERS = (3, 40, 77, 101, 126)    # the entries (mod the bias length) of every q / k bias that make_llama_weights sets to +-16
@@ -79,3 +79,81 @@ def load_llama_weights(model_dir: str) -> StateDict:
         for b in bins:
             sd.update(torch.load(b, map_location="cpu", weights_only=True))
     return {k: v.float() for k, v in sd.items()}
+
+
+# ---------------------------------------------------------------------------------------------- BERT-family sentence encoders
+# names follow transformers' BertModel / XLMRobertaModel (no prefix); a checkpoint saved from a *ForMaskedLM / *ForPreTraining class
+# carries them behind "bert." / "roberta."
+BERT_PREFIXES = ("bert.", "roberta.")
+BERT_IGNORED = ("pooler.", "cls.", "lm_head.")                    # heads the sentence vector does not pass through
+BERT_IGNORED_KEYS = ("embeddings.position_ids", "embeddings.token_type_ids")      # buffers older transformers versions saved
+
+
+def bert_weight_shapes(shape: BertShape) -> Dict[str, tuple]:
+    """Every tensor a BertShape needs, by its transformers name."""
+    h, f = shape.hidden, shape.ffn
+    out = {"embeddings.word_embeddings.weight": (shape.vocab, h), "embeddings.position_embeddings.weight": (shape.max_positions, h),
+           "embeddings.token_type_embeddings.weight": (shape.type_vocab, h), "embeddings.LayerNorm.weight": (h,), "embeddings.LayerNorm.bias": (h,)}
+    for i in range(shape.layers):
+        p = f"encoder.layer.{i}."
+        for nm in ("attention.self.query", "attention.self.key", "attention.self.value", "attention.output.dense"):
+            out[p + nm + ".weight"], out[p + nm + ".bias"] = (h, h), (h,)
+        out[p + "intermediate.dense.weight"], out[p + "intermediate.dense.bias"] = (f, h), (f,)
+        out[p + "output.dense.weight"], out[p + "output.dense.bias"] = (h, f), (h,)
+        for nm in ("attention.output.LayerNorm", "output.LayerNorm"):
+            out[p + nm + ".weight"], out[p + nm + ".bias"] = (h,), (h,)
+    return out
+
+
+def make_bert_weights(shape: BertShape, seed: int = 0) -> StateDict:
+    """Deterministic (torch.Generator, CPU) fp32 weights of a BertShape, in the order of ``bert_weight_shapes``: tables N(0, 0.5^2) /
+    N(0, 0.2^2) for positions and types, projections N(0, 0.04^2) into the attention and the FFN and N(0, 0.02^2) out of them, biases
+    N(0, 0.1^2), LayerNorm 1 + 0.1 N / 0.1 N.  As for the Llama shapes only the seed travels."""
+    g = torch.Generator().manual_seed(seed)
+    sd: StateDict = {}
+    for k, s in bert_weight_shapes(shape).items():
+        if k.endswith("LayerNorm.weight"):
+            sd[k] = 1.0 + torch.randn(*s, generator=g) * 0.1
+        elif k.endswith(".bias"):
+            sd[k] = torch.randn(*s, generator=g) * 0.1
+        elif k.startswith("embeddings."):
+            sd[k] = torch.randn(*s, generator=g) * (0.5 if "word" in k else 0.2)
+        else:
+            sd[k] = torch.randn(*s, generator=g) * (0.02 if k.endswith("output.dense.weight") else 0.04)
+    return sd
+
+
+def map_bert_keys(sd: StateDict, shape: BertShape) -> StateDict:
+    """A checkpoint's tensors under the unprefixed names: a "bert." / "roberta." prefix is dropped, the pooler, the pre-training heads
+    and the saved position_ids / token_type_ids buffers are ignored; any other unknown tensor, a missing one or a wrong shape is an error."""
+    want = bert_weight_shapes(shape)
+    out: StateDict = {}
+    unknown = []
+    for k, v in sd.items():
+        if k.startswith(BERT_IGNORED):
+            continue
+        name = next((k[len(p):] for p in BERT_PREFIXES if k.startswith(p)), k)
+        if name.startswith(BERT_IGNORED) or name in BERT_IGNORED_KEYS:
+            continue
+        if name not in want:
+            unknown.append(k)
+        else:
+            out[name] = v.float()
+    if unknown:
+        raise ValueError(f"the checkpoint has tensors this {shape.model_type} encoder does not apply: {sorted(unknown)[:3]}")
+    missing = sorted(set(want) - set(out))
+    if missing:
+        raise ValueError(f"the checkpoint lacks tensors of this {shape.model_type} encoder: {missing[:3]}")
+    bad = [(k, tuple(out[k].shape), want[k]) for k in want if tuple(out[k].shape) != want[k]]
+    if bad:
+        raise ValueError(f"tensor shapes do not fit config.json: {bad[:3]}")
+    return out
+
+
+def load_bert_weights(model_dir: str, shape: Optional[BertShape] = None) -> StateDict:
+    """A BERT / RoBERTa / XLM-R checkpoint directory (safetensors shards or pytorch_model*.bin) -> the tensors of its shape
+    (``shape``, else the directory's config.json) under the unprefixed names (``map_bert_keys``)."""
+    if shape is None:
+        from .bert_dir import bert_shape_from_config
+        shape = bert_shape_from_config(model_dir)
+    return map_bert_keys(load_llama_weights(model_dir), shape)

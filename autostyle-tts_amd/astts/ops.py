@@ -838,6 +838,54 @@ def qknorm_rope_(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, q_norm_w
     return x
 
 
+@functools.lru_cache(maxsize=None)
+def _bert_lib():
+    from . import _lib_bert
+    return _lib_bert.load()
+
+
+def layernorm_dual(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, want32: bool = True, want16: bool = True,
+                   inplace: bool = False):
+    """LayerNorm over the last axis of ``x`` fp32 ``[..., c]`` (rows may be strided: a column slice of a wider plane) written as fp32
+    and as that same value rounded once to fp16 (astts_op_layernorm_dual, csrc/ops_bert.hip) -> ``(y32, y16)``, None for an output not
+    asked for.  ``inplace``: y32 is ``x`` itself."""
+    assert x.is_cuda and x.dtype == torch.float32 and x.stride(-1) == 1 and (want32 or want16), (x.dtype, x.stride())
+    c = x.shape[-1]
+    for p in (gamma, beta):                                  # the kernel loads c floats from each, 16 bytes at a time
+        assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.shape == (c,), (p.dtype, p.shape)
+    x2 = x if x.dim() == 2 else x.reshape(-1, c)
+    assert x2.data_ptr() == x.data_ptr() or not inplace, "layernorm_dual: in place needs rows at one stride"
+    rows = x2.shape[0]
+    y32 = x2 if inplace else (torch.empty((rows, c), dtype=torch.float32, device=x.device) if want32 else None)
+    y16 = torch.empty((rows, c), dtype=torch.float16, device=x.device) if want16 else None
+    if rows:
+        _lib.check(_bert_lib().astts_op_layernorm_dual(x2.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(y32), _p(y16), rows, c, x2.stride(0),
+                                                       y32.stride(0) if y32 is not None else 0, c, eps, _st()))
+    return (x if inplace else None if y32 is None else y32.view(x.shape)), (None if y16 is None else y16.view(x.shape))
+
+
+def bert_embed_ln(word: torch.Tensor, pos: torch.Tensor, typ: torch.Tensor, ids: torch.Tensor, type_ids: Optional[torch.Tensor],
+                  lens: Optional[torch.Tensor], gamma: torch.Tensor, beta: torch.Tensor, pos_offset: int, eps: float,
+                  want32: bool = True, want16: bool = True):
+    """``LayerNorm(word[ids] + pos[pos_offset + j] + typ[type_ids])`` for the tokens ``j < lens[b]`` of ``ids`` int32 ``[B, T]``, zeros
+    behind them (astts_op_bert_embed_ln) -> ``(out32, out16)`` ``[B, T, c]``, None for an output not asked for.  The tables are fp32
+    and contiguous; ``type_ids`` None: type 0.  The kernel clamps every index into its table; range errors are the caller's to raise."""
+    for tb in (word, pos, typ, gamma, beta):
+        assert tb.is_cuda and tb.dtype == torch.float32 and tb.is_contiguous(), (tb.dtype, tb.shape)
+    assert ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous() and (want32 or want16)
+    assert type_ids is None or (type_ids.is_cuda and type_ids.dtype == torch.int32 and type_ids.shape == ids.shape and type_ids.is_contiguous())
+    b, t = ids.shape
+    assert lens is None or (lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (b,) and lens.is_contiguous())
+    c = word.shape[1]
+    assert pos.shape[1] == c and typ.shape[1] == c and gamma.shape == beta.shape == (c,)
+    o32 = torch.empty((b, t, c), dtype=torch.float32, device=word.device) if want32 else None
+    o16 = torch.empty((b, t, c), dtype=torch.float16, device=word.device) if want16 else None
+    _lib.check(_bert_lib().astts_op_bert_embed_ln(word.data_ptr(), pos.data_ptr(), typ.data_ptr(), ids.data_ptr(), _p(type_ids), _p(lens),
+                                                  gamma.data_ptr(), beta.data_ptr(), _p(o32), _p(o16), b, t, c, word.shape[0], pos.shape[0],
+                                                  typ.shape[0], int(pos_offset), eps, _st()))
+    return o32, o16
+
+
 def argmax_rows(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """fp32 ``[rows, n]`` (row stride >= n: a column slice of a wider plane is read in place) -> int32 ``[rows]`` (ties: the lowest
     index), on the device: the greedy step's token."""
